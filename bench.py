@@ -6,7 +6,13 @@ default camera (rx = ry = 0, zoom 2, frame 0), v1 scene (sceneSDF -> manySphere,
 volumeRender_kernel.cu:222).  One "step" = one frame of that workload rendered to
 device memory (and, for N > 1, gathered to rank 0 and assembled).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, renders W warmup frames, times K frames, writes the last timed frame and
+the timed calls' counters to DIR when --dump-outputs is given (dump_outputs below), and prints
+the result line.  Everything else described here -- the parity check of the timed frames,
+config.single_frame / spin / random_poses / fp32x3 / group, roofline.traffic_live and
+cpu_baseline -- runs after that under --full only; a plain run reports those fields as null.
+
 The K frames of the timed region go through nr_render_batch: the persistent tracer's
 pixel queue deals 64-pixel chunks to the frames in turn (up to 32 frames per launch), so
 one frame's longest rays march while other frames' pixels keep the matrix cores busy --
@@ -84,6 +90,14 @@ def parse():
     ap.add_argument("--size", type=int, default=None)
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--geometry", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed frames, also run everything else the bench measures or checks: the "
+                         "parity check of every timed frame, config.single_frame / spin / random_poses / fp32x3 / "
+                         "group, roofline.traffic_live and cpu_baseline (each with its own --no-... switch); a "
+                         "plain run times the headline only and reports those fields as null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed frames, write what they returned to DIR: frame.npy (the last timed "
+                         "frame's RGBA channels, float32) and stats.npy (the counters of the timed calls, float64)")
     ap.add_argument("--no-fp32x3", action="store_true",
                     help="skip config.fp32x3 (the same frames timed in NR_PRECISION_FP32X3)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -106,7 +120,31 @@ def parse():
         if getattr(a, k) is None:
             setattr(a, k, v)
     a.replicas = a.config == "c5"
+    if not a.full:   # a plain run: set up, warm up, time the K frames, print the line
+        a.no_fp32x3 = a.no_cpu_baseline = a.no_live_traffic = a.no_single_frame = True
+        a.no_spin = a.no_random_poses = a.no_group = True
     return a
+
+
+DUMP_LIMIT = 48 << 20  # bytes --dump-outputs writes at most: a larger frame is sampled (16 B a pixel + 8 B its index)
+
+
+def dump_outputs(path, frame, stats):
+    """--dump-outputs: what the last timed step handed its caller.  frame.npy: the last timed
+    frame's pixels (uint32 a<<24|b<<16|g<<8|r, row-major) as float32 channels [n, 4] (r, g, b, a in
+    0..255), every pixel of the frame in order -- or, where that exceeds DUMP_LIMIT bytes, the
+    pixels at the sorted flat indices default_rng(0) draws (without replacement), the indices
+    themselves in frame_index.npy (float64).  stats.npy: the ray-steps and shade evals the timed
+    calls counted (float64 [2], summed over the timed frames and ranks)."""
+    os.makedirs(path, exist_ok=True)
+    px = np.ascontiguousarray(frame, np.uint32).reshape(-1)
+    if px.size * 16 > DUMP_LIMIT:
+        idx = np.sort(np.random.default_rng(0).choice(px.size, DUMP_LIMIT // 24, replace=False))
+        np.save(os.path.join(path, "frame_index.npy"), idx.astype(np.float64))
+        px = px[idx]
+    np.save(os.path.join(path, "frame.npy"),
+            ((px[:, None] >> np.arange(0, 32, 8, dtype=np.uint32)) & 0xff).astype(np.float32))
+    np.save(os.path.join(path, "stats.npy"), np.asarray(stats, np.float64))
 
 
 def cpu_model():
@@ -316,8 +354,13 @@ def main_group(a):
     dt = time.perf_counter() - t0
     rs[0].set_profiling(False)
     prof = rs[0].prof_collect()
-    ref = torch.from_numpy(rs[0].render(size, size, a.max_steps, with_stats=False).view(np.int32).reshape(-1)).to("cuda:0")
-    parity = all(bool(torch.equal(frames[i], ref)) for i in range(a.steps))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, frames[a.steps - 1].cpu().numpy().view(np.uint32),
+                     [counted["ray_steps"], counted["shade_evals"]])
+    parity = None
+    if a.full:
+        ref = torch.from_numpy(rs[0].render(size, size, a.max_steps, with_stats=False).view(np.int32).reshape(-1)).to("cuda:0")
+        parity = all(bool(torch.equal(frames[i], ref)) for i in range(a.steps))
     launches = max(prof["march_launches"], 1)
     march_avg_ms = prof["march_ms"] / launches
     # rank 0's k_trace launches render shard 0: its share of the counted work (1 / n of the rows)
@@ -337,7 +380,7 @@ def main_group(a):
             "parallelism": f"nr_group (one process, C ABI): row-band shards x{n} (band {BAND}), one RCCL gather "
                            f"per call of <= {MAX_BATCH} frames, NR_GROUP_ASYNC (call k+1 renders while call k's "
                            f"shards travel), re-interleave on GPU 0",
-            "parity_vs_single_gpu_render": parity, "parity_frames_checked": a.steps,
+            "parity_vs_single_gpu_render": parity, "parity_frames_checked": a.steps if a.full else 0,
         },
         "roofline": {"bound": "mfma", "kernel": "k_trace (batched instance, GPU 0's shard)",
                      "achieved": round(achieved, 3), "peak": peak, "unit": "TFLOP/s",
@@ -358,7 +401,7 @@ def group_child(a):
     bounded by a time limit: the C-ABI multi-GPU path measured on the node the driver runs."""
     cmd = [sys.executable, os.path.abspath(__file__), "--group", "--gpus", str(a.gpus), "--steps", str(a.steps),
            "--warmup", str(a.warmup), "--config", a.config, "--precision", a.precision, "--size", str(a.size),
-           "--max-steps", str(a.max_steps), "--no-cpu-baseline"]
+           "--max-steps", str(a.max_steps), "--full", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK",
                         "ROLE_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
@@ -530,7 +573,10 @@ def main():
 
     dt, prof, ray_steps_k, shade_evals_k, per_rank = timed(run_batched, True)
     rank_steps = per_rank[:, 1]
-    parity, nchecked = check_frames(a.steps, default_cams)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, frames[a.steps - 1][: size * size].cpu().numpy().view(np.uint32),
+                     [ray_steps_k, shade_evals_k])
+    parity, nchecked = check_frames(a.steps, default_cams) if a.full else (None, 0)
 
     dt_single = None
     if not a.no_single_frame:

@@ -65,6 +65,43 @@ def test_config_presets(monkeypatch):
     assert a.replicas and a.geometry is None and (a.size, a.precision) == (2048, "fp16")
 
 
+def test_plain_run_is_headline_only(monkeypatch):
+    """Without --full every extra measurement is off; --full turns them on, each still switchable."""
+    extras = ("no_fp32x3", "no_cpu_baseline", "no_live_traffic", "no_single_frame", "no_spin", "no_random_poses",
+              "no_group")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    assert all(getattr(a, k) for k in extras)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-spin", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and a.no_spin
+    assert not any(getattr(a, k) for k in extras if k != "no_spin")
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: the frame's channels as float32 in pixel order, the counters as float64; above
+    DUMP_LIMIT the same seeded sample of pixels every time, with its indices."""
+    import numpy as np
+    frame = (np.arange(40, dtype=np.uint32) * np.uint32(0x01030507)).astype(np.int32).view(np.uint32).reshape(5, 8)
+    d = str(tmp_path / "out")
+    bench.dump_outputs(d, frame, [123.0, 45.0])
+    assert sorted(os.listdir(d)) == ["frame.npy", "stats.npy"]
+    f, s = np.load(os.path.join(d, "frame.npy")), np.load(os.path.join(d, "stats.npy"))
+    assert f.dtype == np.float32 and f.shape == (40, 4) and s.dtype == np.float64 and s.tolist() == [123.0, 45.0]
+    back = sum(f[:, c].astype(np.uint32) << np.uint32(8 * c) for c in range(4))
+    assert np.array_equal(back, frame.reshape(-1))
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 24 * 10)   # 16 B of channels + 8 B of index per sampled pixel
+    d2 = str(tmp_path / "sampled")
+    bench.dump_outputs(d2, frame, [1, 2])
+    idx = np.load(os.path.join(d2, "frame_index.npy"))
+    assert idx.dtype == np.float64 and len(idx) == 10 and np.all(np.diff(idx) > 0)
+    assert idx.nbytes + np.load(os.path.join(d2, "frame.npy")).nbytes <= bench.DUMP_LIMIT
+    assert np.array_equal(np.load(os.path.join(d2, "frame.npy")), f[idx.astype(int)])
+    bench.dump_outputs(str(tmp_path / "again"), frame, [1, 2])
+    assert np.array_equal(np.load(os.path.join(str(tmp_path / "again"), "frame_index.npy")), idx)
+
+
 def test_c5_rank_geometries():
     """c5: rank r renders bundled geometry r % 5 (BASELINE configs[4], one geometry per GPU)."""
     g = [bench.GEOMS[r % len(bench.GEOMS)] for r in range(8)]

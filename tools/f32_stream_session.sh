@@ -13,7 +13,7 @@ if [ -z "$NOTESTS" ]; then
     --timeout 200 --timeout-method thread > "$OUT/tests.log" 2>&1 || exit 1
 fi
 timeout -k 10 240 python -u tools/mlp_latency.py > "$OUT/latency.log" 2>&1 || exit 1
-run() { timeout -k 10 400 python -u bench.py --steps 10 --warmup 3 2>&1 | grep '^{'; }
+run() { timeout -k 10 400 python -u bench.py --full --steps 10 --warmup 3 2>&1 | grep '^{'; }
 echo "== stream" > "$OUT/ab.log"; NR_LIBRARY=$PWD/build/f32stream/libnr.so run >> "$OUT/ab.log" || exit 1
 echo "== default (loop)" >> "$OUT/ab.log"; run >> "$OUT/ab.log" || exit 1
 echo "== stream (again)" >> "$OUT/ab.log"; NR_LIBRARY=$PWD/build/f32stream/libnr.so run >> "$OUT/ab.log" || exit 1

@@ -11,7 +11,7 @@ TAG=${1:-r1}
 REPO=$(pwd)
 OUT=$(realpath -m "gpurun_out/prof_$TAG")
 mkdir -p "$OUT"
-timeout -k 10 300 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/ktrace" -o run -- \
     python3 "$REPO/bench.py" --no-cpu-baseline --no-live-traffic --no-single-frame --no-random-poses --warmup 32 > "$OUT/ktrace_bench.json" 2> "$OUT/ktrace.err"

@@ -11,7 +11,7 @@ if [ -z "$NOTESTS" ]; then
     tests/test_gpu_lowp.py tests/test_gpu_fp32x3.py -x -v -s --timeout 200 --timeout-method thread > "$OUT/tests.log" 2>&1 || exit 1
 fi
 run() {
-  timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 2>&1 | grep '^{' || return 1
+  timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 2>&1 | grep '^{' || return 1
   timeout -k 10 300 python -u tools/config_bench.py --frames 6 --only C3,C4-full,C5 --endgame 0,0.001 2>&1 | grep '^{' || return 1
 }
 echo "== default (reload)" > "$OUT/ab.log"; run >> "$OUT/ab.log" || exit 1
