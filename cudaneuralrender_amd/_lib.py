@@ -19,6 +19,8 @@ NR_HOST, NR_DEVICE = 0, 1
 NR_SCHEDULE = {"persistent": 0, "wavefront": 1, "layered": 2}
 NR_GROUP_COPY, NR_GROUP_ASYNC = 1, 2
 NR_ENDGAME_DEFAULT = 0.001  # include/neural_render.h: the bf16/fp16 endgame threshold by default
+# status of a queried ray (nr_trace_rays, nr_render_gbuffer)
+NR_RAY_MISS, NR_RAY_ESCAPED, NR_RAY_HIT, NR_RAY_LIMIT = 0, 1, 2, 3
 
 # every symbol include/neural_render.h declares
 EXPORTS = [
@@ -33,6 +35,7 @@ EXPORTS = [
     "nr_h5_dims", "nr_h5_read_f32",
     "nr_group_create", "nr_group_destroy", "nr_group_size", "nr_group_render_batch", "nr_pack_x3",
     "nr_set_endgame", "nr_group_create_ex", "nr_group_synchronize", "nr_group_layout",
+    "nr_trace_rays", "nr_render_gbuffer",
 ]
 
 
@@ -116,6 +119,8 @@ def lib():
         "nr_set_scene": (I, [P, I]),
         "nr_set_matcap": (I, [P, P, I, I]),
         "nr_render": (I, [P, P, I, I, I, I, ctypes.POINTER(NRStats)]),
+        "nr_trace_rays": (I, [P, P, P, L64, I, P, P, P, P, P, I, ctypes.POINTER(NRStats)]),
+        "nr_render_gbuffer": (I, [P, I, I, I, P, P, P, P, P, I, ctypes.POINTER(NRStats)]),
         "nr_render_shard": (I, [P, P, I, I, I, I, I, I, I, ctypes.POINTER(NRStats)]),
         "nr_render_batch": (I, [P, ctypes.POINTER(NRFrame), I, I, I, I, I, I, I, I, ctypes.POINTER(NRStats)]),
         "nr_group_create": (I, [ctypes.POINTER(P), I, ctypes.POINTER(P)]),

@@ -80,6 +80,11 @@ struct nr_ctx {
     long long order_key = -1;  // image configuration the stored order belongs to
     unsigned long long *d_stamps = nullptr;
     size_t n_stamps = 0;       // waves of the last traced launch
+    // ray queries (nr_trace_rays, nr_render_gbuffer): the ray cursor on its own 128-byte line +
+    // 4 x u64 stats; staging of host rays and results
+    uint32_t *d_qs = nullptr;
+    float *d_qio = nullptr;
+    size_t cap_qio = 0;
 
     // settings
     float inv_view[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 2};
@@ -836,6 +841,7 @@ int nr_destroy(nr_ctx *c) {
     dfree(c->d_SP); dfree(c->d_SD); dfree(c->d_ctr); dfree(c->d_out); dfree(c->d_tr); dfree(c->d_stamps); dfree(c->d_bcost); dfree(c->d_order[0]); dfree(c->d_order[1]); dfree(c->d_io); dfree(c->d_matcap);
     dfree(c->d_rargs); dfree(c->d_lsdf); dfree(c->d_lz);
     dfree(c->d_frames); dfree(c->d_bout);
+    dfree(c->d_qs); dfree(c->d_qio);
     if (c->h_frames) (void)hipHostFree(c->h_frames);
     if (c->ev_frames) (void)hipEventDestroy(c->ev_frames);
     if (c->h_ctr) (void)hipHostFree(c->h_ctr);
@@ -1284,6 +1290,102 @@ int nr_render_shard(nr_ctx *c, uint32_t *out, int W, int H, int band, int nshard
 
 int nr_render(nr_ctx *c, uint32_t *out, int W, int H, int max_steps, int loc, nr_stats *stats) {
     return nr_render_shard(c, out, W, H, H > 0 ? H : 1, 1, 0, max_steps, loc, stats);
+}
+
+// Ray queries: n caller-supplied rays (origins / dirs), or with origins == NULL the W x H pixel
+// rays of the context's view, through one k_query launch (nr_query.hip).  Always the fp32 MLP.
+static int query_rays(nr_ctx *c, const char *fn, const float *origins, const float *dirs, long n, int W, int H,
+                      int max_steps, int32_t *status, int32_t *steps, float *t, float *position, float *normal, int loc,
+                      nr_stats *stats) {
+    if (c->dims.empty()) return set_err(c, NR_E_STATE, "%s: no network loaded", fn);
+    if (!c->fused)
+        return set_err(c, NR_E_FORMAT, "%s: ray queries need a [3|4, 32, ..., 32, 1] network (no layered fallback)", fn);
+    nr_stats st{};
+    if (n == 0) { if (stats) *stats = st; return NR_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    if (!c->d_qs) HIPCHK(c, hipMalloc(&c->d_qs, 128 + 4 * 8));
+    QueryArgs Q{};
+    Q.n = n; Q.W = W; Q.H = H;
+    Q.inv_w = 1.0 / (double)W;
+    Q.rcp_w = pow2_rcp(W); Q.rcp_h = pow2_rcp(H);
+    memcpy(Q.inv_view, c->inv_view, sizeof Q.inv_view);
+    Q.max_steps = max_steps; Q.scene = c->scene; Q.frame = c->frame;
+    Q.cursor = c->d_qs;
+    Q.stats = reinterpret_cast<unsigned long long *>(c->d_qs + 32);
+    Q.origins = origins; Q.dirs = dirs;
+    Q.status = status; Q.steps = steps; Q.t = t; Q.position = position; Q.normal = normal;
+    const size_t N = (size_t)n;
+    if (loc != NR_DEVICE) {
+        // staging, in floats: the rays, then every output the caller asked for
+        const size_t need = (origins ? 6 * N : 0) + (status ? N : 0) + (steps ? N : 0) + (t ? N : 0) +
+                            (position ? 3 * N : 0) + (normal ? 3 * N : 0);
+        int rc;
+        if ((rc = ensure_buf(c, c->d_qio, c->cap_qio, need)) != NR_OK) return rc;
+        float *q = c->d_qio;
+        if (origins) {
+            HIPCHK(c, hipMemcpyAsync(q, origins, 3 * N * 4, hipMemcpyHostToDevice, s));
+            HIPCHK(c, hipMemcpyAsync(q + 3 * N, dirs, 3 * N * 4, hipMemcpyHostToDevice, s));
+            Q.origins = q; Q.dirs = q + 3 * N;
+            q += 6 * N;
+        }
+        if (status) { Q.status = reinterpret_cast<int32_t *>(q); q += N; }
+        if (steps) { Q.steps = reinterpret_cast<int32_t *>(q); q += N; }
+        if (t) { Q.t = q; q += N; }
+        if (position) { Q.position = q; q += 3 * N; }
+        if (normal) { Q.normal = q; q += 3 * N; }
+    }
+    // the grid by the CU count, as the frame tracer's: nr_set_occupancy's workgroups per CU, or 2
+    // (one launch of rays is a single frame's worth: the tail outweighs the bulk, default_bpc)
+    const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : 2;
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + 255) / 256, (size_t)num_cus(c->device) * bpc));
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, hipMemsetAsync(c->d_qs, 0, 128 + 4 * 8, s));
+    HIPCHK(c, launch_query(Q, c->mlp16, grid, s));
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (loc != NR_DEVICE) {
+        if (status) HIPCHK(c, hipMemcpyAsync(status, Q.status, N * 4, hipMemcpyDeviceToHost, s));
+        if (steps) HIPCHK(c, hipMemcpyAsync(steps, Q.steps, N * 4, hipMemcpyDeviceToHost, s));
+        if (t) HIPCHK(c, hipMemcpyAsync(t, Q.t, N * 4, hipMemcpyDeviceToHost, s));
+        if (position) HIPCHK(c, hipMemcpyAsync(position, Q.position, 3 * N * 4, hipMemcpyDeviceToHost, s));
+        if (normal) HIPCHK(c, hipMemcpyAsync(normal, Q.normal, 3 * N * 4, hipMemcpyDeviceToHost, s));
+    }
+    if (stats) {
+        unsigned long long hs[4];
+        HIPCHK(c, hipMemcpyAsync(hs, Q.stats, sizeof hs, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        st.ray_steps = hs[0];
+        st.rays_hit = hs[1];
+        st.iterations = (int32_t)hs[2];
+        st.rays_shaded = hs[3];
+        st.shade_evals = normal ? 4ull * hs[3] : 0ull;
+        st.launches = 2;
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        st.ms_total = ms;
+        *stats = st;
+    } else if (loc != NR_DEVICE) {
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    return NR_OK;
+}
+
+int nr_trace_rays(nr_ctx *c, const float *origins, const float *dirs, long n, int max_steps, int32_t *status,
+                  int32_t *steps, float *t, float *position, float *normal, int loc, nr_stats *stats) {
+    if (!c) return set_err(nullptr, NR_E_INVALID, "nr_trace_rays: ctx is NULL");
+    if (n < 0 || n > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_trace_rays: n = %ld outside [0, 2^30]", n);
+    if (max_steps < 1) return set_err(c, NR_E_INVALID, "nr_trace_rays: max_steps < 1");
+    if (n > 0 && (!origins || !dirs)) return set_err(c, NR_E_INVALID, "nr_trace_rays: NULL rays");
+    return query_rays(c, "nr_trace_rays", origins, dirs, n, 1, 1, max_steps, status, steps, t, position, normal, loc, stats);
+}
+
+int nr_render_gbuffer(nr_ctx *c, int W, int H, int max_steps, int32_t *status, int32_t *steps, float *t, float *position,
+                      float *normal, int loc, nr_stats *stats) {
+    if (!c) return set_err(nullptr, NR_E_INVALID, "nr_render_gbuffer: ctx is NULL");
+    if (W < 1 || H < 1 || (long)W * H > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_render_gbuffer: bad size %dx%d", W, H);
+    if (max_steps < 1) return set_err(c, NR_E_INVALID, "nr_render_gbuffer: max_steps < 1");
+    return query_rays(c, "nr_render_gbuffer", nullptr, nullptr, (long)W * H, W, H, max_steps, status, steps, t, position,
+                      normal, loc, stats);
 }
 
 int nr_assemble_shards(nr_ctx *c, const uint32_t *src, size_t stride, uint32_t *dst, int W, int H, int band,

@@ -148,7 +148,24 @@ struct TraceArgs {
                                 // instances stage it in LDS beside the 16-bit pack (NR_EG_WAVES)
 };
 
+// Ray queries (nr_query.hip; nr_trace_rays, nr_render_gbuffer): n rays, each writing its own slot
+// of the outputs that are not NULL.
+struct QueryArgs {
+    const float *origins, *dirs;  // [n][3]; both NULL: the pixel rays of the W x H view below
+    long n;                       // <= 2^30
+    int W, H;
+    double inv_w;                 // 1/W for udiv_r
+    float rcp_w, rcp_h;           // pow2_rcp(W), pow2_rcp(H) (pixel_uv)
+    float inv_view[12];
+    int max_steps, scene, frame;
+    int32_t *status, *steps;      // NR_RAY_*, iterations taken
+    float *t, *position, *normal; // [n], [n][3], [n][3]; normal NULL: no tetrahedron evaluations
+    uint32_t *cursor;             // next ray to deal (zeroed before the launch)
+    unsigned long long *stats;    // [0] ray-steps, [1] rays that entered the sphere, [2] max steps, [3] hits
+};
+
 int dense_lds_bytes(int in, int out);
+hipError_t launch_query(const QueryArgs &Q, const MlpArgs &M, int grid, hipStream_t st);
 hipError_t launch_dense(const DenseArgs &D, int src, int grid, hipStream_t st);
 hipError_t launch_init_f(const RenderArgs &A, const FrameArgs *F, const QueueArgs &Q, long npix, long total,
                          int grid, hipStream_t st);

@@ -360,6 +360,56 @@ class Renderer:
         self._chk(self._L.nr_assemble_shards(self._ctx, ctypes.c_void_p(src_ptr), stride, ctypes.c_void_p(dst_ptr),
                                              W, H, band, nshards, NR_DEVICE))
 
+    # -- ray queries / geometry buffers
+    @staticmethod
+    def _query_outputs(shape, normals):
+        return {"status": np.zeros(shape, np.int32), "steps": np.zeros(shape, np.int32),
+                "t": np.zeros(shape, np.float32), "position": np.zeros(shape + (3,), np.float32),
+                "normal": np.zeros(shape + (3,), np.float32) if normals else None}
+
+    def trace_rays(self, origins, dirs, max_steps=6000, normals=True, with_stats=False):
+        """nr_trace_rays on host arrays: march the rays p = origins[i] + t * dirs[i] (dirs as given,
+        not normalised) as nr_render marches a pixel ray.  Returns a dict of numpy arrays: status
+        (NR_RAY_*), steps, t, position (n, 3) and normal (n, 3); normals=False skips the normal
+        evaluations and leaves "normal" out (shadow / occlusion rays).  Always the fp32 MLP."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError(f"origins {o.shape} and dirs {d.shape} differ")
+        n = o.shape[0]
+        out = self._query_outputs((n,), normals)
+        st = NRStats()
+        self._chk(self._L.nr_trace_rays(self._ctx, o.ctypes.data, d.ctypes.data, n, int(max_steps),
+                                        *[a.ctypes.data if a is not None else None for a in out.values()], NR_HOST,
+                                        ctypes.byref(st) if with_stats else None))
+        if not normals:
+            del out["normal"]
+        return (out, st.as_dict()) if with_stats else out
+
+    def trace_rays_device(self, origins_ptr, dirs_ptr, n, max_steps=6000, status_ptr=None, steps_ptr=None, t_ptr=None,
+                          position_ptr=None, normal_ptr=None, with_stats=False):
+        """nr_trace_rays on device buffers (e.g. torch tensors' data_ptr(): float32 [n, 3] rays,
+        int32 status / steps, float32 t, [n, 3] position / normal); None = that output is not wanted.
+        Runs on the context's stream (set_stream) and, without stats, returns without waiting."""
+        vp = [ctypes.c_void_p(p) if p else None
+              for p in (origins_ptr, dirs_ptr, status_ptr, steps_ptr, t_ptr, position_ptr, normal_ptr)]
+        st = NRStats()
+        self._chk(self._L.nr_trace_rays(self._ctx, vp[0], vp[1], int(n), int(max_steps), *vp[2:], NR_DEVICE,
+                                        ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
+    def render_gbuffer(self, W, H, max_steps=6000, normals=True, with_stats=False):
+        """nr_render_gbuffer: the trace_rays outputs for the W x H pixel rays of the current view,
+        shaped (H, W) and (H, W, 3); status == NR_RAY_HIT exactly where render() colours the pixel."""
+        out = self._query_outputs((H, W), normals)
+        st = NRStats()
+        self._chk(self._L.nr_render_gbuffer(self._ctx, W, H, int(max_steps),
+                                            *[a.ctypes.data if a is not None else None for a in out.values()], NR_HOST,
+                                            ctypes.byref(st) if with_stats else None))
+        if not normals:
+            del out["normal"]
+        return (out, st.as_dict()) if with_stats else out
+
     def mlp_forward(self, X):
         X = np.ascontiguousarray(X, np.float32)
         info = self.mlp_info()

@@ -24,6 +24,8 @@ extern "C" {
 #endif
 
 #define NR_ABI_VERSION 3   /* 2: nr_stats.endgame_evals, nr_set_endgame (round 5); 3: nr_stats.endgame_switches (round 6) */
+/* (nr_trace_rays / nr_render_gbuffer are new symbols only -- no struct or existing signature changed --
+ * so the version stays 3) */
 
 /* status codes */
 #define NR_OK 0
@@ -147,6 +149,45 @@ int nr_render(nr_ctx *ctx, uint32_t *out, int W, int H, int max_steps, int out_l
  * of nr_render. */
 int nr_render_shard(nr_ctx *ctx, uint32_t *out, int W, int H, int band_rows,
                     int nshards, int shard, int max_steps, int out_loc, nr_stats *stats);
+
+/* ---- ray queries / geometry buffers ------------------------------------------ */
+/* status of a queried ray */
+#define NR_RAY_MISS    0  /* never entered the bounding sphere (r = 1.2) */
+#define NR_RAY_ESCAPED 1  /* marched out of it (tfar exhausted): a background pixel */
+#define NR_RAY_HIT     2  /* converged (tstep < 1e-6) with an iteration left to shade: a coloured pixel */
+#define NR_RAY_LIMIT   3  /* max_steps reached, or converged in the last iteration */
+
+/* Marches n caller-supplied rays through the scene exactly as nr_render marches a pixel ray
+ * (initMarcher's entry, singleMarch's step, surfaceNormal's tetrahedron) and returns the geometry
+ * instead of a colour, in one persistent launch.  Ray i is p = origins[i] + t * dirs[i]; dirs is
+ * used as given (not normalised).  Entry: no root of the bounding sphere -> MISS; else tnear =
+ * max(tnear, 0), p = o + d * tnear, tfar = the far root (tnear is not subtracted, as in the
+ * reference).  Iteration it = 0 .. max_steps - 1: tstep = sceneSDF(p, mlp(p)); tfar -= tstep, tfar
+ * <= 0 -> ESCAPED; p += d * tstep, travel += tstep; tstep < 1e-6 -> HIT when it + 1 < max_steps,
+ * else LIMIT; steps = it + 1 in all three.  A ray still live after max_steps iterations is LIMIT
+ * with steps = max_steps.  A HIT has position = p, t = tnear + travel and normal = the normalised
+ * tetrahedral gradient at p (epsilon 1e-5); every other status has t, position and normal +0.0 and
+ * a MISS has steps 0.
+ * Any output pointer may be NULL.  With normal == NULL the four tetrahedron evaluations per hit
+ * are not run and stats->shade_evals is 0 (occlusion / shadow rays).
+ * Scene and frame are the context's (nr_set_scene, nr_set_view); a 4-input network gets
+ * (float)frame as its 4th input.  The MLP is always the fp32 one (bit-exact with the CPU oracle):
+ * nr_set_precision is ignored, as NR_SCHED_LAYERED ignores it.  A ray's results depend only on
+ * that ray: they are the same bits for any n, order or split into calls.
+ * loc = NR_HOST or NR_DEVICE for all the pointers.  stats (may be NULL): ray_steps = sum of steps,
+ * rays_hit = rays that entered the sphere, rays_shaded = HITs, shade_evals = 4 per HIT (0 without
+ * normals), iterations = the largest steps.
+ * Errors: NR_E_INVALID (ctx NULL, n < 0, n > 2^30, max_steps < 1, origins / dirs NULL with n > 0),
+ * NR_E_STATE (no network), NR_E_FORMAT (a network the fused kernels do not take: there is no
+ * layered fallback for queries).  n = 0 returns NR_OK without a launch. */
+int nr_trace_rays(nr_ctx *ctx, const float *origins /*[n][3]*/, const float *dirs /*[n][3]*/, long n,
+                  int max_steps, int32_t *status, int32_t *steps, float *t,
+                  float *position /*[n][3]*/, float *normal /*[n][3]*/, int loc, nr_stats *stats);
+/* The same query for the W x H pixel rays of the context's view (nr_set_view), generated in the
+ * kernel: pixel (x, y) is at index y * W + x and its ray is nr_render's.  status == NR_RAY_HIT
+ * exactly where nr_render's pixel is coloured.  NR_E_INVALID also for W or H < 1 or W * H > 2^30. */
+int nr_render_gbuffer(nr_ctx *ctx, int W, int H, int max_steps, int32_t *status, int32_t *steps, float *t,
+                      float *position, float *normal, int loc, nr_stats *stats);
 
 /* Batched frames (persistent schedule): render nframes frames -- each with its own camera
  * (the nr_set_view matrices), frame number and output image -- of the same size/shard
