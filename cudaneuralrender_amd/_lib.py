@@ -36,6 +36,7 @@ EXPORTS = [
     "nr_group_create", "nr_group_destroy", "nr_group_size", "nr_group_render_batch", "nr_pack_x3",
     "nr_set_endgame", "nr_group_create_ex", "nr_group_synchronize", "nr_group_layout",
     "nr_trace_rays", "nr_render_gbuffer",
+    "nr_sample_grid", "nr_mesh_grid", "nr_extract_mesh", "nr_obj_save",
 ]
 
 
@@ -121,6 +122,11 @@ def lib():
         "nr_render": (I, [P, P, I, I, I, I, ctypes.POINTER(NRStats)]),
         "nr_trace_rays": (I, [P, P, P, L64, I, P, P, P, P, P, I, ctypes.POINTER(NRStats)]),
         "nr_render_gbuffer": (I, [P, I, I, I, P, P, P, P, P, I, ctypes.POINTER(NRStats)]),
+        "nr_sample_grid": (I, [P, FP, FP, IP, P, I, ctypes.POINTER(NRStats)]),
+        "nr_mesh_grid": (I, [P, P, FP, FP, IP, F, P, L64, P, L64, ctypes.POINTER(L64), ctypes.POINTER(L64), I]),
+        "nr_extract_mesh": (I, [P, FP, FP, IP, F, P, P, L64, P, L64, ctypes.POINTER(L64), ctypes.POINTER(L64), I,
+                                ctypes.POINTER(NRStats)]),
+        "nr_obj_save": (I, [ctypes.c_char_p, P, L64, P, P, L64]),
         "nr_render_shard": (I, [P, P, I, I, I, I, I, I, I, ctypes.POINTER(NRStats)]),
         "nr_render_batch": (I, [P, ctypes.POINTER(NRFrame), I, I, I, I, I, I, I, I, ctypes.POINTER(NRStats)]),
         "nr_group_create": (I, [ctypes.POINTER(P), I, ctypes.POINTER(P)]),

@@ -85,6 +85,16 @@ struct nr_ctx {
     uint32_t *d_qs = nullptr;
     float *d_qio = nullptr;
     size_t cap_qio = 0;
+    // volume sampling and isosurface extraction (nr_sample_grid, nr_mesh_grid, nr_extract_mesh):
+    // the lattice of nr_extract_mesh (4 B per point; the staging of host lattices too), the
+    // extraction's scratch (MeshArgs: 4 B per point + 24 B per 256 points) and the staging of
+    // host meshes
+    float *d_grid = nullptr;
+    size_t cap_grid = 0;
+    unsigned long long *d_mesh = nullptr;
+    size_t cap_mesh = 0;
+    float *d_mio = nullptr;
+    size_t cap_mio = 0;
 
     // settings
     float inv_view[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 2};
@@ -842,6 +852,7 @@ int nr_destroy(nr_ctx *c) {
     dfree(c->d_rargs); dfree(c->d_lsdf); dfree(c->d_lz);
     dfree(c->d_frames); dfree(c->d_bout);
     dfree(c->d_qs); dfree(c->d_qio);
+    dfree(c->d_grid); dfree(c->d_mesh); dfree(c->d_mio);
     if (c->h_frames) (void)hipHostFree(c->h_frames);
     if (c->ev_frames) (void)hipEventDestroy(c->ev_frames);
     if (c->h_ctr) (void)hipHostFree(c->h_ctr);
@@ -1386,6 +1397,226 @@ int nr_render_gbuffer(nr_ctx *c, int W, int H, int max_steps, int32_t *status, i
     if (max_steps < 1) return set_err(c, NR_E_INVALID, "nr_render_gbuffer: max_steps < 1");
     return query_rays(c, "nr_render_gbuffer", nullptr, nullptr, (long)W * H, W, H, max_steps, status, steps, t, position,
                       normal, loc, stats);
+}
+
+// ---- volume sampling and isosurface extraction (nr_mesh.hip) ----
+
+// The lattice arguments: every dim >= min_dim and at most 2^30 points.
+static int lattice_check(nr_ctx *c, const char *fn, const float *origin, const float *step, const int *dims, int min_dim) {
+    if (!origin || !step || !dims) return set_err(c, NR_E_INVALID, "%s: NULL lattice arguments", fn);
+    long n = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < min_dim) return set_err(c, NR_E_INVALID, "%s: dims[%d] = %d < %d", fn, a, dims[a], min_dim);
+        n *= dims[a];  // (at most 2^30 * 2^31 before the test)
+        if (n > (1l << 30)) return set_err(c, NR_E_INVALID, "%s: more than 2^30 lattice points", fn);
+    }
+    return NR_OK;
+}
+
+static int fused_check(nr_ctx *c, const char *fn) {
+    if (c->dims.empty()) return set_err(c, NR_E_STATE, "%s: no network loaded", fn);
+    if (!c->fused)
+        return set_err(c, NR_E_FORMAT, "%s: volume sampling needs a [3|4, 32, ..., 32, 1] network (no layered fallback)", fn);
+    return NR_OK;
+}
+
+// One k_grid launch over the lattice into d_sdf.  The grid by the CU count: nr_set_occupancy's
+// workgroups per CU, or 12 as nr_mlp_forward's (more than fit at once, so that they start staggered)
+static int grid_launch(nr_ctx *c, const LatticeArgs &L, float *d_sdf, hipStream_t s) {
+    GridArgs G{};
+    G.L = L;
+    G.scene = c->scene;
+    G.frame = c->frame;
+    G.sdf = d_sdf;
+    const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : 12;
+    const size_t N = (size_t)L.n;
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + 255) / 256, (size_t)num_cus(c->device) * bpc));
+    HIPCHK(c, launch_grid(G, c->mlp16, grid, s));
+    return NR_OK;
+}
+
+// Count, scan and (with output buffers of sufficient capacity) emit over the device lattice d_sdf;
+// with `normals` the vertex normals too.  *launches counts the kernels issued.
+static int mesh_run(nr_ctx *c, const char *fn, hipStream_t s, const LatticeArgs &L, const float *d_sdf, float iso,
+                    float *vertices, float *normals, long v_cap, int32_t *triangles, long t_cap, long *nv, long *nt,
+                    int loc, int *launches) {
+    const size_t N = (size_t)L.n;
+    const size_t nblk = (N + 255) / 256;
+    // scratch, in 8-byte words: totals [2], scans [2][nblk], block counts [2][nblk] u32, point words [N] u32
+    const size_t need = 2 + 2 * nblk + nblk + (N + 1) / 2;
+    int rc;
+    if ((rc = ensure_buf(c, c->d_mesh, c->cap_mesh, need)) != NR_OK) return rc;
+    MeshArgs A{};
+    A.L = L;
+    A.sdf = d_sdf;
+    A.iso = iso;
+    A.nblk = (int)nblk;
+    A.total = c->d_mesh;
+    A.off = c->d_mesh + 2;
+    A.cnt = reinterpret_cast<uint32_t *>(c->d_mesh + 2 + 2 * nblk);
+    A.word = A.cnt + 2 * nblk;
+    HIPCHK(c, launch_mesh_count(A, s));
+    *launches += 2;
+    unsigned long long tot[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(tot, A.total, sizeof tot, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    *nv = (long)tot[0];
+    *nt = (long)tot[1];
+    if (tot[0] > (unsigned long long)INT32_MAX)
+        return set_err(c, NR_E_INVALID, "%s: %llu vertices do not fit 32-bit indices", fn, tot[0]);
+    if (!vertices && !triangles) return NR_OK;  // count only
+    if (!vertices || !triangles) return set_err(c, NR_E_INVALID, "%s: vertices and triangles are given together", fn);
+    if (v_cap < *nv || t_cap < *nt)
+        return set_err(c, NR_E_NOMEM, "%s: %ld vertices / %ld triangles exceed the capacities %ld / %ld", fn, *nv, *nt,
+                       v_cap, t_cap);
+    if (tot[0] == 0) return NR_OK;  // (no crossing edge: no triangle either)
+    const size_t V3 = 3 * (size_t)tot[0], T3 = 3 * (size_t)tot[1];
+    float *dv = vertices, *dn = normals;
+    int32_t *dt = triangles;
+    if (loc != NR_DEVICE) {
+        if ((rc = ensure_buf(c, c->d_mio, c->cap_mio, V3 * (normals ? 2 : 1) + T3)) != NR_OK) return rc;
+        dv = c->d_mio;
+        dn = normals ? dv + V3 : nullptr;
+        dt = reinterpret_cast<int32_t *>(dv + V3 * (normals ? 2 : 1));
+    }
+    A.vertices = dv;
+    A.triangles = dt;
+    HIPCHK(c, launch_mesh_emit(A, s));
+    *launches += 1;
+    if (normals) {
+        VNormalArgs V{};
+        V.vertices = dv;
+        V.normals = dn;
+        V.nv = (long)tot[0];
+        V.scene = c->scene;
+        V.frame = c->frame;
+        // 64 vertices per workgroup and pass
+        const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : 4;
+        const int grid = (int)std::max<size_t>(1, std::min<size_t>(((size_t)tot[0] + 63) / 64, (size_t)num_cus(c->device) * bpc));
+        HIPCHK(c, launch_vnormal(V, c->mlp16, grid, s));
+        *launches += 1;
+    }
+    if (loc != NR_DEVICE) {
+        HIPCHK(c, hipMemcpyAsync(vertices, dv, V3 * 4, hipMemcpyDeviceToHost, s));
+        if (normals) HIPCHK(c, hipMemcpyAsync(normals, dn, V3 * 4, hipMemcpyDeviceToHost, s));
+        if (T3) HIPCHK(c, hipMemcpyAsync(triangles, dt, T3 * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    return NR_OK;
+}
+
+int nr_sample_grid(nr_ctx *c, const float origin[3], const float step[3], const int dims[3], float *sdf, int loc,
+                   nr_stats *stats) {
+    if (!c) return set_err(nullptr, NR_E_INVALID, "nr_sample_grid: ctx is NULL");
+    if (!sdf) return set_err(c, NR_E_INVALID, "nr_sample_grid: sdf is NULL");
+    int rc;
+    if ((rc = lattice_check(c, "nr_sample_grid", origin, step, dims, 1)) != NR_OK) return rc;
+    if ((rc = fused_check(c, "nr_sample_grid")) != NR_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const LatticeArgs L = make_lattice(origin, step, dims);
+    const size_t N = (size_t)L.n;
+    float *d = sdf;
+    if (loc != NR_DEVICE) {
+        if ((rc = ensure_buf(c, c->d_grid, c->cap_grid, N)) != NR_OK) return rc;
+        d = c->d_grid;
+    }
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    if ((rc = grid_launch(c, L, d, s)) != NR_OK) return rc;
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (loc != NR_DEVICE) HIPCHK(c, hipMemcpyAsync(sdf, d, N * 4, hipMemcpyDeviceToHost, s));
+    if (stats) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        nr_stats st{};
+        st.ray_steps = N;
+        st.launches = 1;
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        st.ms_total = ms;
+        *stats = st;
+    } else if (loc != NR_DEVICE) {
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    return NR_OK;
+}
+
+int nr_mesh_grid(nr_ctx *c, const float *sdf, const float origin[3], const float step[3], const int dims[3], float iso,
+                 float *vertices, long v_cap, int32_t *triangles, long t_cap, long *nv, long *nt, int loc) {
+    if (!c) return set_err(nullptr, NR_E_INVALID, "nr_mesh_grid: ctx is NULL");
+    if (!sdf || !nv || !nt) return set_err(c, NR_E_INVALID, "nr_mesh_grid: NULL sdf, nv or nt");
+    *nv = 0;
+    *nt = 0;
+    int rc;
+    if ((rc = lattice_check(c, "nr_mesh_grid", origin, step, dims, 2)) != NR_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const LatticeArgs L = make_lattice(origin, step, dims);
+    const float *d = sdf;
+    if (loc != NR_DEVICE) {
+        if ((rc = ensure_buf(c, c->d_grid, c->cap_grid, (size_t)L.n)) != NR_OK) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->d_grid, sdf, (size_t)L.n * 4, hipMemcpyHostToDevice, s));
+        d = c->d_grid;
+    }
+    int launches = 0;
+    return mesh_run(c, "nr_mesh_grid", s, L, d, iso, vertices, nullptr, v_cap, triangles, t_cap, nv, nt, loc, &launches);
+}
+
+int nr_extract_mesh(nr_ctx *c, const float origin[3], const float step[3], const int dims[3], float iso, float *vertices,
+                    float *normals, long v_cap, int32_t *triangles, long t_cap, long *nv, long *nt, int loc,
+                    nr_stats *stats) {
+    if (!c) return set_err(nullptr, NR_E_INVALID, "nr_extract_mesh: ctx is NULL");
+    if (!nv || !nt) return set_err(c, NR_E_INVALID, "nr_extract_mesh: NULL nv or nt");
+    *nv = 0;
+    *nt = 0;
+    int rc;
+    if ((rc = lattice_check(c, "nr_extract_mesh", origin, step, dims, 2)) != NR_OK) return rc;
+    if ((rc = fused_check(c, "nr_extract_mesh")) != NR_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const LatticeArgs L = make_lattice(origin, step, dims);
+    if ((rc = ensure_buf(c, c->d_grid, c->cap_grid, (size_t)L.n)) != NR_OK) return rc;
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    if ((rc = grid_launch(c, L, c->d_grid, s)) != NR_OK) return rc;
+    int launches = 1;
+    const bool with_normals = normals && vertices && triangles;
+    rc = mesh_run(c, "nr_extract_mesh", s, L, c->d_grid, iso, vertices, with_normals ? normals : nullptr, v_cap, triangles,
+                  t_cap, nv, nt, loc, &launches);
+    if (rc != NR_OK) return rc;
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (stats) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        nr_stats st{};
+        st.ray_steps = (uint64_t)L.n;
+        st.rays_shaded = (uint64_t)*nv;
+        st.shade_evals = with_normals ? 4ull * (uint64_t)*nv : 0ull;
+        st.launches = launches;
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        st.ms_total = ms;
+        *stats = st;
+    }
+    return NR_OK;
+}
+
+int nr_obj_save(const char *path, const float *vertices, long nv, const float *normals, const int32_t *triangles,
+                long nt) {
+    if (!path || nv < 0 || nt < 0 || (nv > 0 && !vertices) || (nt > 0 && !triangles))
+        return set_err(nullptr, NR_E_INVALID, "nr_obj_save: bad arguments");
+    FILE *f = fopen(path, "w");
+    if (!f) return set_err(nullptr, NR_E_IO, "nr_obj_save: cannot open %s", path);
+    for (long i = 0; i < nv; ++i)
+        fprintf(f, "v %.9g %.9g %.9g\n", (double)vertices[3 * i], (double)vertices[3 * i + 1], (double)vertices[3 * i + 2]);
+    if (normals)
+        for (long i = 0; i < nv; ++i)
+            fprintf(f, "vn %.9g %.9g %.9g\n", (double)normals[3 * i], (double)normals[3 * i + 1], (double)normals[3 * i + 2]);
+    for (long i = 0; i < nt; ++i) {
+        const long a = (long)triangles[3 * i] + 1, b = (long)triangles[3 * i + 1] + 1, d = (long)triangles[3 * i + 2] + 1;
+        if (normals) fprintf(f, "f %ld//%ld %ld//%ld %ld//%ld\n", a, a, b, b, d, d);
+        else fprintf(f, "f %ld %ld %ld\n", a, b, d);
+    }
+    const bool bad = ferror(f) != 0;
+    if (fclose(f) != 0 || bad) return set_err(nullptr, NR_E_IO, "nr_obj_save: write to %s failed", path);
+    return NR_OK;
 }
 
 int nr_assemble_shards(nr_ctx *c, const uint32_t *src, size_t stride, uint32_t *dst, int W, int H, int band,

@@ -164,7 +164,60 @@ struct QueryArgs {
     unsigned long long *stats;    // [0] ray-steps, [1] rays that entered the sphere, [2] max steps, [3] hits
 };
 
+// The lattice of nr_sample_grid / nr_mesh_grid / nr_extract_mesh: point (i, j, k) has linear index
+// (k ny + j) nx + i and coordinates origin[a] + (float)idx_a * step[a] (one f32 multiply, one add).
+struct LatticeArgs {
+    float origin[3], step[3];
+    int nx, ny, nz;
+    long n;                       // nx ny nz <= 2^30
+    double inv_nx, inv_nxy;       // 1/nx, 1/(nx ny) for udiv_r
+};
+inline LatticeArgs make_lattice(const float *origin, const float *step, const int *dims) {
+    LatticeArgs L{};
+    for (int a = 0; a < 3; ++a) { L.origin[a] = origin[a]; L.step[a] = step[a]; }
+    L.nx = dims[0]; L.ny = dims[1]; L.nz = dims[2];
+    L.n = (long)dims[0] * dims[1] * dims[2];
+    L.inv_nx = 1.0 / (double)L.nx;
+    L.inv_nxy = 1.0 / ((double)L.nx * (double)L.ny);
+    return L;
+}
+
+// Volume sampling (nr_mesh.hip k_grid): sdf[idx] = sceneSDF(p, mlp(p)) over the lattice.
+struct GridArgs {
+    LatticeArgs L;
+    int scene, frame;
+    float *sdf;                   // [n]
+};
+
+// Isosurface extraction (nr_mesh.hip k_mesh_count / k_mesh_scan / k_mesh_emit) over 256-point
+// blocks of the lattice's linear index.
+struct MeshArgs {
+    LatticeArgs L;
+    const float *sdf;             // [n]
+    float iso;
+    int nblk;                     // ceil(n / 256)
+    uint32_t *word;               // [n]: bits 0-6 the point's vertex mask (edge slots), 7-17 the vertices
+                                  // and 18-29 the triangles of its block before it
+    uint32_t *cnt;                // [2][nblk]: vertices, triangles of each block
+    unsigned long long *off;      // [2][nblk]: their exclusive scans
+    unsigned long long *total;    // [2]: vertices, triangles
+    float *vertices;              // [nv][3]
+    int32_t *triangles;           // [nt][3]
+};
+
+// Vertex normals (nr_mesh.hip k_vnormal): the normalised tetrahedral gradient at each vertex.
+struct VNormalArgs {
+    const float *vertices;        // [nv][3]
+    float *normals;               // [nv][3]
+    long nv;
+    int scene, frame;
+};
+
 int dense_lds_bytes(int in, int out);
+hipError_t launch_grid(const GridArgs &G, const MlpArgs &M, int grid, hipStream_t st);
+hipError_t launch_vnormal(const VNormalArgs &V, const MlpArgs &M, int grid, hipStream_t st);
+hipError_t launch_mesh_count(const MeshArgs &A, hipStream_t st);  // k_mesh_count, then k_mesh_scan
+hipError_t launch_mesh_emit(const MeshArgs &A, hipStream_t st);
 hipError_t launch_query(const QueryArgs &Q, const MlpArgs &M, int grid, hipStream_t st);
 hipError_t launch_dense(const DenseArgs &D, int src, int grid, hipStream_t st);
 hipError_t launch_init_f(const RenderArgs &A, const FrameArgs *F, const QueueArgs &Q, long npix, long total,

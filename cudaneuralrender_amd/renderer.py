@@ -81,6 +81,26 @@ def save_ppm(path, img):
     check(lib().nr_ppm_save(path.encode(), img.ctypes.data, img.shape[1], img.shape[0]))
 
 
+def save_obj(path, vertices, triangles, normals=None):
+    """nr_obj_save: a Wavefront OBJ of the mesh (V [nv, 3] float32, T [nt, 3] int32, optional per-vertex
+    normals [nv, 3]); floats are printed with %.9g, which round-trips float32."""
+    V = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    T = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+    N = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if N is not None and N.shape != V.shape:
+        raise ValueError(f"normals {N.shape} and vertices {V.shape} differ")
+    check(lib().nr_obj_save(str(path).encode(), V.ctypes.data, V.shape[0], None if N is None else N.ctypes.data,
+                            T.ctypes.data, T.shape[0]))
+
+
+def _lattice(origin, step, dims):
+    """(origin, step, dims) as the C arrays of the lattice calls"""
+    o = np.ascontiguousarray(origin, np.float32).reshape(3)
+    s = np.ascontiguousarray(step, np.float32).reshape(3)
+    d = (ctypes.c_int * 3)(*[int(v) for v in dims])
+    return o, s, d
+
+
 def pack_x3(dims, kernels, biases):
     """The library's fp32x3 pack of a fused-shape network (nr_pack_x3; host only): (a_ops uint16,
     floats float32, ok).  For the test oracle's emulation of the fp32x3 MLP (the bf16/fp16 tracers'
@@ -410,6 +430,76 @@ class Renderer:
             del out["normal"]
         return (out, st.as_dict()) if with_stats else out
 
+    # -- volume sampling / isosurface extraction
+    def sample_grid(self, origin, step, dims, with_stats=False):
+        """nr_sample_grid: the scene's distance at the lattice points origin + (i, j, k) * step,
+        dims = (nx, ny, nz), generated in the kernel.  Returns float32 [nz, ny, nx].  Always the
+        fp32 MLP."""
+        o, s, d = _lattice(origin, step, dims)
+        out = np.zeros((d[2], d[1], d[0]), np.float32)
+        st = NRStats()
+        self._chk(self._L.nr_sample_grid(self._ctx, _fptr(o), _fptr(s), d, out.ctypes.data, NR_HOST,
+                                         ctypes.byref(st) if with_stats else None))
+        return (out, st.as_dict()) if with_stats else out
+
+    def sample_grid_device(self, sdf_ptr, origin, step, dims, with_stats=False):
+        """nr_sample_grid into a device buffer of nx * ny * nz float32 (e.g. a torch tensor's
+        data_ptr()).  Runs on the context's stream (set_stream) and, without stats, returns without
+        waiting."""
+        o, s, d = _lattice(origin, step, dims)
+        st = NRStats()
+        self._chk(self._L.nr_sample_grid(self._ctx, _fptr(o), _fptr(s), d, ctypes.c_void_p(sdf_ptr), NR_DEVICE,
+                                         ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
+    def mesh_grid(self, sdf, origin, step, iso=0.0):
+        """nr_mesh_grid: marching tetrahedra over the lattice values sdf [nz, ny, nx] (any values; no
+        network needed).  Returns (V [nv, 3] float32, T [nt, 3] int32): a count-only call first, then
+        the buffers are allocated."""
+        sdf = np.ascontiguousarray(sdf, np.float32)
+        if sdf.ndim != 3:
+            raise ValueError(f"sdf must be [nz, ny, nx], got {sdf.shape}")
+        o, s, d = _lattice(origin, step, sdf.shape[::-1])
+        nv, nt = ctypes.c_long(0), ctypes.c_long(0)
+
+        def call(V, T):
+            return self._L.nr_mesh_grid(self._ctx, sdf.ctypes.data, _fptr(o), _fptr(s), d, float(iso),
+                                        None if V is None else V.ctypes.data, 0 if V is None else V.shape[0],
+                                        None if T is None else T.ctypes.data, 0 if T is None else T.shape[0],
+                                        ctypes.byref(nv), ctypes.byref(nt), NR_HOST)
+
+        self._chk(call(None, None))
+        V, T = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
+        if nv.value:
+            self._chk(call(V, T))
+        return V, T
+
+    def extract_mesh(self, origin, step, dims, iso=0.0, normals=True, with_stats=False):
+        """nr_extract_mesh: sample the lattice on the device and mesh it.  Returns a dict with
+        "vertices" [nv, 3] float32, "triangles" [nt, 3] int32 and, with normals=True, "normals"
+        [nv, 3] (the normalised tetrahedral gradient at each vertex).  The count-only call comes first
+        (it samples the lattice too), then the buffers are allocated."""
+        o, s, d = _lattice(origin, step, dims)
+        nv, nt = ctypes.c_long(0), ctypes.c_long(0)
+        st = NRStats()
+
+        def call(V, N, T):
+            return self._L.nr_extract_mesh(self._ctx, _fptr(o), _fptr(s), d, float(iso),
+                                           None if V is None else V.ctypes.data, None if N is None else N.ctypes.data,
+                                           0 if V is None else V.shape[0], None if T is None else T.ctypes.data,
+                                           0 if T is None else T.shape[0], ctypes.byref(nv), ctypes.byref(nt), NR_HOST,
+                                           ctypes.byref(st) if with_stats else None)
+
+        self._chk(call(None, None, None))
+        V, T = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
+        N = np.zeros((nv.value, 3), np.float32) if normals else None
+        if nv.value:
+            self._chk(call(V, N, T))
+        out = {"vertices": V, "triangles": T}
+        if normals:
+            out["normals"] = N
+        return (out, st.as_dict()) if with_stats else out
+
     def mlp_forward(self, X):
         X = np.ascontiguousarray(X, np.float32)
         info = self.mlp_info()
@@ -429,7 +519,7 @@ class Renderer:
         return Z
 
 
-__all__ = ["Renderer", "camera", "pack_x3", "read_keras_h5", "load_png", "save_png", "save_ppm", "shard_rows",
+__all__ = ["Renderer", "camera", "pack_x3", "read_keras_h5", "load_png", "save_png", "save_ppm", "save_obj", "shard_rows",
            "assemble_shards", "NR_COLOR_FACING", "NR_COLOR_MATCAP"]
 
 

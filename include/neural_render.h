@@ -189,6 +189,73 @@ int nr_trace_rays(nr_ctx *ctx, const float *origins /*[n][3]*/, const float *dir
 int nr_render_gbuffer(nr_ctx *ctx, int W, int H, int max_steps, int32_t *status, int32_t *steps, float *t,
                       float *position, float *normal, int loc, nr_stats *stats);
 
+/* ---- volume sampling / isosurface extraction ------------------------------------ */
+/* (new symbols only, as the ray queries: NR_ABI_VERSION stays 3)
+ *
+ * The lattice of the three calls: dims = (nx, ny, nz); point (i, j, k), 0 <= i < nx and likewise j,
+ * k, has linear index (k * ny + j) * nx + i and coordinates origin[a] + (float)idx_a * step[a] --
+ * one f32 multiply, then one f32 add.  At most 2^30 points.
+ *
+ * nr_sample_grid writes sdf[idx] = sceneSDF(p, mlp(p)) for every lattice point, generated in the
+ * kernel (no point list), with the context's scene and frame (nr_set_scene, nr_set_view); a 4-input
+ * network gets (float)frame as its 4th input.  Always the fp32 MLP (bit-exact with the CPU oracle):
+ * nr_set_precision is ignored, as for the ray queries.  A point's value depends only on that point:
+ * the same bits for any grid size, occupancy or lattice that contains the point.  sdf is
+ * [nz][ny][nx], a host or device pointer per loc.  stats (may be NULL): ray_steps = points
+ * evaluated, launches, ms_total.
+ * Errors: NR_E_INVALID (a NULL argument, a dim < 1, nx * ny * nz > 2^30), NR_E_STATE (no network),
+ * NR_E_FORMAT (a network the fused kernels do not take, as for the ray queries). */
+int nr_sample_grid(nr_ctx *ctx, const float origin[3], const float step[3], const int dims[3],
+                   float *sdf /*[nz][ny][nx]*/, int loc, nr_stats *stats);
+/* Marching tetrahedra over a caller-supplied lattice of values (any values: it needs no network and
+ * works on a context without one).  loc applies to every pointer but nv / nt.  The output is a pure
+ * function of the inputs -- counts, an exclusive scan and an emit pass; no atomic decides an order:
+ *  1. Inside.  A corner is inside iff s < iso: NaN is outside, and so is s == iso.
+ *  2. Tetrahedra.  Each cell (i, j, k), i < nx - 1 and likewise j, k, is split into the 6 Kuhn
+ *     tetrahedra: for each permutation (a, b, c) of the axes, in lexicographic order xyz, xzy, yxz,
+ *     yzx, zxy, zyx, the path v0 = the cell's corner 000, v1 = v0 + e_a, v2 = v1 + e_b, v3 = v2 + e_c
+ *     = its corner 111.
+ *  3. Vertices.  One per lattice edge whose endpoints differ in insideness.  The edges are the 7
+ *     kinds the split uses, from a lattice point o to o + e for e in this slot order: 100, 010, 001,
+ *     110, 101, 011, 111 (x first); both ends must lie in the lattice.  Vertices are numbered by
+ *     increasing index(o) * 7 + slot.  With a = o and b = o + e: t = (iso - s_a) / (s_b - s_a) and
+ *     pos = p_a + (p_b - p_a) * t per component, all f32 with one rounding per operation (p_a, p_b
+ *     the lattice coordinates above); a NaN coordinate is written as the quiet NaN 0x7fc00000.  As a
+ *     is always the lower lattice end, every tetrahedron sharing the edge gets the same vertex.
+ *  4. Triangles.  A tetrahedron with one inside corner P and outside corners Q1 < Q2 < Q3 (by path
+ *     index) emits one triangle on the edges (P,Q1), (P,Q2), (P,Q3); likewise with inside and
+ *     outside exchanged.  One with inside corners A < B and outside corners C < D emits two, {AC, AD,
+ *     BD} and {AC, BD, BC} (the diagonal joins AC and BD).  The winding is decided on the topology,
+ *     not on floats: with every vertex moved to the midpoint of its edge, (b - a) x (c - a) points
+ *     from the centroid of the inside corners towards the centroid of the outside corners.
+ *     Triangles are written in increasing cell index ((k * ny + j) * nx + i of the cell's corner
+ *     000); within a cell the order is fixed -- the same on every call -- but not specified, and so
+ *     is the vertex a triangle starts with.
+ *  5. Capacities.  *nv and *nt are always set.  With vertices == NULL && triangles == NULL the call
+ *     only counts.  If v_cap < *nv or t_cap < *nt nothing is written and the call returns
+ *     NR_E_NOMEM.
+ *  6. Errors.  NR_E_INVALID: a NULL ctx, sdf, origin, step, dims, nv or nt; only one of vertices /
+ *     triangles NULL; a dim < 2; nx * ny * nz > 2^30; more than 2^31 - 1 vertices.
+ * Scratch: the context keeps 4 B per lattice point + 24 B per 256 points of device memory for the
+ * passes (and, for loc = NR_HOST, staging for the lattice and the mesh) until nr_destroy. */
+int nr_mesh_grid(nr_ctx *ctx, const float *sdf /*[nz][ny][nx]*/, const float origin[3], const float step[3],
+                 const int dims[3], float iso, float *vertices /*[v_cap][3]*/, long v_cap,
+                 int32_t *triangles /*[t_cap][3]*/, long t_cap, long *nv, long *nt, int loc);
+/* nr_sample_grid into a context-owned device buffer (4 B per lattice point, kept until nr_destroy),
+ * then nr_mesh_grid on it: capacities, counting call (which samples too) and errors as both.  If
+ * normals is given (with vertices and triangles), vertex i gets the world normal of
+ * nr_trace_rays' hits at its position: the normalised tetrahedral gradient, epsilon 1e-5, in the
+ * same arithmetic.  stats (may be NULL): ray_steps = lattice points, rays_shaded = *nv, shade_evals
+ * = 4 * *nv with normals, else 0; launches, ms_total. */
+int nr_extract_mesh(nr_ctx *ctx, const float origin[3], const float step[3], const int dims[3], float iso,
+                    float *vertices /*[v_cap][3]*/, float *normals /*[v_cap][3] or NULL*/, long v_cap,
+                    int32_t *triangles /*[t_cap][3]*/, long t_cap, long *nv, long *nt, int loc, nr_stats *stats);
+/* Wavefront OBJ writer (host only, host pointers): "v x y z" per vertex and, when normals is given,
+ * "vn x y z", printed with %.9g (which round-trips f32); faces "f a b c", or "f a//a b//b c//c" with
+ * normals, 1-based.  NR_E_IO when the file cannot be opened or written. */
+int nr_obj_save(const char *path, const float *vertices /*[nv][3]*/, long nv, const float *normals /*or NULL*/,
+                const int32_t *triangles /*[nt][3]*/, long nt);
+
 /* Batched frames (persistent schedule): render nframes frames -- each with its own camera
  * (the nr_set_view matrices), frame number and output image -- of the same size/shard
  * in as few launches as possible (up to 32 frames per launch).  The pixel queue runs
