@@ -37,6 +37,7 @@ EXPORTS = [
     "nr_set_endgame", "nr_group_create_ex", "nr_group_synchronize", "nr_group_layout",
     "nr_trace_rays", "nr_render_gbuffer",
     "nr_sample_grid", "nr_mesh_grid", "nr_extract_mesh", "nr_obj_save",
+    "nr_mlp_gradient",
 ]
 
 
@@ -140,6 +141,7 @@ def lib():
         "nr_batch_frames_per_launch": (I, [I, I, I, I, I, I, I]),
         "nr_assemble_shards": (I, [P, P, ctypes.c_size_t, P, I, I, I, I, I]),
         "nr_mlp_forward": (I, [P, P, P, L64, I]),
+        "nr_mlp_gradient": (I, [P, P, L64, P, P, P, I, ctypes.POINTER(NRStats)]),
         "nr_layer_forward": (I, [P, I, P, P, L64, I]),
         "nr_camera": (I, [F, F, F, F, F, FP, FP]),
         "nr_camera_ex": (I, [F, F, F, F, F, I, FP, FP]),

@@ -41,6 +41,8 @@ struct nr_ctx {
     bool fused = false;
     int precision = NR_PRECISION_FP32;
     float *d_pack16 = nullptr;
+    float *d_gpack16 = nullptr;  // the backward pack (pack_grad_16; nr_mlp_gradient), null: none
+    int gpack_bytes = 0;
     uint16_t *d_lp16 = nullptr;
     uint16_t *d_x3lp = nullptr;  // bf16/fp16: the fp32x3 pack for the normals (MlpArgs::x3n)
     float *d_x3fl = nullptr;
@@ -193,7 +195,7 @@ int free_network(nr_ctx *c) {
     for (auto *p : c->d_W) (void)hipFree(p);
     for (auto *p : c->d_b) (void)hipFree(p);
     c->d_W.clear(); c->d_b.clear();
-    dfree(c->d_pack16); dfree(c->d_lp16); dfree(c->d_lpf16); dfree(c->d_x3lp); dfree(c->d_x3fl);
+    dfree(c->d_pack16); dfree(c->d_gpack16); dfree(c->d_lp16); dfree(c->d_lpf16); dfree(c->d_x3lp); dfree(c->d_x3fl);
     dfree(c->d_lps16); dfree(c->d_lpfs16);
     c->fused = false;
     if (c->lgraph) { (void)hipGraphExecDestroy(c->lgraph); c->lgraph = nullptr; }
@@ -306,6 +308,16 @@ int set_network(nr_ctx *c, std::vector<int> dims, std::vector<std::vector<float>
         c->mlp16.pk_bytes = (int)pb;
         c->mlp16.in0 = c->dims[0];
         c->mlp16.nh = nl - 2;
+        // the backward pack beside it (networks of at most GRAD_MAX_HIDDEN hidden layers)
+        std::vector<float> gpack;
+        c->gpack_bytes = 0;
+        if (pack_grad_16(c->dims, c->kernels, gpack)) {
+            const size_t gb = (gpack.size() * 4 + 15) / 16 * 16;
+            gpack.resize(gb / 4, 0.0f);
+            HIPCHK(c, hipMalloc(&c->d_gpack16, gb));
+            HIPCHK(c, hipMemcpy(c->d_gpack16, gpack.data(), gb, hipMemcpyHostToDevice));
+            c->gpack_bytes = (int)gb;
+        }
     }
     return upload_lowp(c);
 }
@@ -1717,6 +1729,68 @@ int nr_mlp_forward(nr_ctx *c, const float *X, float *Y, long n, int loc) {
     }
     if (loc != NR_DEVICE) {
         HIPCHK(c, hipMemcpyAsync(Y, dY, (size_t)n * outn * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    return NR_OK;
+}
+
+// The analytic gradient: one k_grad launch (nr_grad.hip).  Always the fp32 MLP.
+constexpr int GRAD_BPC = 12;  // workgroups per CU of its grid by default
+int nr_mlp_gradient(nr_ctx *c, const float *X, long n, float *value, float *grad, float *normal, int loc,
+                    nr_stats *stats) {
+    if (!c) return set_err(nullptr, NR_E_INVALID, "nr_mlp_gradient: ctx is NULL");
+    if (n < 0 || n > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_mlp_gradient: n = %ld outside [0, 2^30]", n);
+    if (n > 0 && !X) return set_err(c, NR_E_INVALID, "nr_mlp_gradient: X is NULL");
+    if (!value && !grad && !normal) return set_err(c, NR_E_INVALID, "nr_mlp_gradient: every output is NULL");
+    if (c->dims.empty()) return set_err(c, NR_E_STATE, "nr_mlp_gradient: no network loaded");
+    if (!c->fused)
+        return set_err(c, NR_E_FORMAT, "nr_mlp_gradient: needs a [3|4, 32, ..., 32, 1] network (no layered fallback)");
+    if (!c->d_gpack16)
+        return set_err(c, NR_E_FORMAT, "nr_mlp_gradient: more than %d hidden 32 x 32 layers", GRAD_MAX_HIDDEN);
+    nr_stats st{};
+    if (n == 0) { if (stats) *stats = st; return NR_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const size_t N = (size_t)n, in0 = (size_t)c->dims[0];
+    GradArgs G{};
+    G.X = X; G.n = n;
+    G.value = value; G.grad = grad; G.normal = normal;
+    G.gb = c->d_gpack16; G.gb_bytes = c->gpack_bytes;
+    if (loc != NR_DEVICE) {
+        // staging, in floats: the points, then every output the caller asked for
+        const size_t need = N * in0 + (value ? N : 0) + (grad ? N * in0 : 0) + (normal ? 3 * N : 0);
+        int rc;
+        if ((rc = ensure_buf(c, c->d_io, c->cap_io, need)) != NR_OK) return rc;
+        float *q = c->d_io;
+        HIPCHK(c, hipMemcpyAsync(q, X, N * in0 * 4, hipMemcpyHostToDevice, s));
+        G.X = q; q += N * in0;
+        if (value) { G.value = q; q += N; }
+        if (grad) { G.grad = q; q += N * in0; }
+        if (normal) { G.normal = q; q += 3 * N; }
+    }
+    const MlpArgs M = c->mlp16;
+    if (grad_lds_bytes(M, G) > 64 * 1024) return set_err(c, NR_E_FORMAT, "nr_mlp_gradient: the packs exceed 64 KB of LDS");
+    // two workgroups per CU are resident (their LDS: the two packs); the grid by the CU count:
+    // nr_set_occupancy's workgroups per CU, or GRAD_BPC
+    const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : GRAD_BPC;
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + 255) / 256, (size_t)num_cus(c->device) * bpc));
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, launch_grad(G, M, grid, s));
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (loc != NR_DEVICE) {
+        if (value) HIPCHK(c, hipMemcpyAsync(value, G.value, N * 4, hipMemcpyDeviceToHost, s));
+        if (grad) HIPCHK(c, hipMemcpyAsync(grad, G.grad, N * in0 * 4, hipMemcpyDeviceToHost, s));
+        if (normal) HIPCHK(c, hipMemcpyAsync(normal, G.normal, 3 * N * 4, hipMemcpyDeviceToHost, s));
+    }
+    if (stats) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        st.ray_steps = (uint64_t)n;
+        st.launches = 1;
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        st.ms_total = ms;
+        *stats = st;
+    } else if (loc != NR_DEVICE) {
         HIPCHK(c, hipStreamSynchronize(s));
     }
     return NR_OK;

@@ -44,6 +44,27 @@ constexpr int MAX_HIDDEN = 16;
 NR_HD constexpr inline int pk_final(int nh) { return PK_HID + nh * PK_HID_STRIDE; }
 NR_HD constexpr inline int pk_floats(int nh) { return pk_final(nh) + 36; }
 
+// Backward (gradient) pack beside the fp32 one (pack_grad_16; nr_grad.hip), in floats, raw
+// (unscaled) weights.  The backward pass of hidden layer j is the forward's MFMA loop on the
+// transposed kernel: row (A operand) = the layer's input unit, k = its output unit, so every
+// chain runs over the output units 0..31 ascending.  The gradient of register k of lane group g
+// belongs to unit 4k + g -- the order the forward's masks of layers 0..nh-1 are in, and the
+// order a C result is the next B operand in; the last ReLU layer's mask (units 8g + k in the
+// forward) is transposed once per tile.
+//   per hidden layer j (0..nh-1), base j*1024:
+//              A operand           [m >> 2][lane 64][m & 3]   (m = 2 * k-step + row tile), lane
+//                                  (i, kk): K_(j+1)[in = 16mt + 4(i & 3) + (i >> 2)][out = 4st + kk]
+//   gb_l0(nh): K_0 transposed, one row tile [k-step >> 2][lane 64][k-step & 3], lane (i, kk):
+//              K_0[in = i & 3][out = 4st + kk] (0 for i & 3 >= dims[0]): rows repeat every 4, so
+//              every lane group's C registers 0..3 hold the point's gradient
+//   gb_last(nh): the last kernel [group 4][register 8] = K_last[4k + g]
+// The masks of the nh + 1 ReLU layers are 8 bits per lane, tile and layer in two 32-bit words,
+// hence GRAD_MAX_HIDDEN.
+constexpr int GRAD_MAX_HIDDEN = 7;
+NR_HD constexpr inline int gb_l0(int nh) { return nh * 1024; }
+NR_HD constexpr inline int gb_last(int nh) { return gb_l0(nh) + 512; }
+NR_HD constexpr inline int gb_floats(int nh) { return gb_last(nh) + 32; }
+
 // Low-precision (bf16/fp16) pack for the 32-point-tile MLP (nr_mlp16.h, mlp32_lowp):
 // v_mfma_f32_32x32x16_{bf16,f16}, lane l = (row / point r = l & 31, half h = l >> 5).
 // 16-bit elements (a_ops):
@@ -94,6 +115,10 @@ bool fused_shape_ok(const std::vector<int> &dims);
 // pack_fp32_16: clamp (if not null) = 1 when the pack is scaled for the clamped ReLU
 bool pack_fp32_16(const std::vector<int> &dims, const std::vector<std::vector<float>> &kernels,
                   const std::vector<std::vector<float>> &biases, std::vector<float> &pack, int *clamp = nullptr);
+// the backward pack (above); false if the shape is not fused or has more than GRAD_MAX_HIDDEN
+// hidden 32 x 32 layers
+bool pack_grad_16(const std::vector<int> &dims, const std::vector<std::vector<float>> &kernels,
+                  std::vector<float> &pack);
 bool pack_lowp_32(const std::vector<int> &dims, const std::vector<std::vector<float>> &kernels,
                   const std::vector<std::vector<float>> &biases, int precision,
                   std::vector<uint16_t> &a_ops, std::vector<float> &bias, int *clamp = nullptr);

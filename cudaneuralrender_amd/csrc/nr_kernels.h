@@ -213,7 +213,18 @@ struct VNormalArgs {
     int scene, frame;
 };
 
+// Analytic gradient (nr_grad.hip k_grad): every point writes its slot of the outputs that are not NULL.
+struct GradArgs {
+    const float *X;               // [n][in0]
+    long n;                       // <= 2^30
+    float *value, *grad, *normal; // [n], [n][in0], [n][3]
+    const float *gb;              // the backward pack (nr_internal.h pack_grad_16), staged after the fp32 pack
+    int gb_bytes;
+};
+
 int dense_lds_bytes(int in, int out);
+int grad_lds_bytes(const MlpArgs &M, const GradArgs &G);  // one k_grad workgroup's dynamic LDS
+hipError_t launch_grad(const GradArgs &G, const MlpArgs &M, int grid, hipStream_t st);  // 4-wave workgroups
 hipError_t launch_grid(const GridArgs &G, const MlpArgs &M, int grid, hipStream_t st);
 hipError_t launch_vnormal(const VNormalArgs &V, const MlpArgs &M, int grid, hipStream_t st);
 hipError_t launch_mesh_count(const MeshArgs &A, hipStream_t st);  // k_mesh_count, then k_mesh_scan

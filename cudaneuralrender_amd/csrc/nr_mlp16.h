@@ -115,11 +115,16 @@ __device__ __forceinline__ void f32_hidden7_stream(const float *s, float (&a)[NT
 // the chains of the next layer map to the same values).  Every VALU instruction costs f32
 // matrix time on gfx950 (profiles/r1_mfma_peak.txt), and this halves the activation VALU.
 // NH == 7 (the caller checks nh == 7): the stream below for NT <= 2 with the clamped ReLU
-template <int NT, int PART = 0, bool CL = false, int NH = 0>
+// MK (nr_grad.hip; nh <= GRAD_MAX_HIDDEN): mk[t] receives tile t's ReLU masks, z > 0 of ReLU
+// layer l's register k in bit 8 (l & 3) + k of word l >> 2 (mk zeroed by the caller).  Both ReLU
+// forms give +0 exactly where z <= 0 (z is never -0: its chain starts from +0) and a positive
+// value elsewhere, so the bit is min(bits of the activation, 1): v_min_u32 + v_lshl_or_b32.
+template <int NT, int PART = 0, bool CL = false, int NH = 0, bool MK = false>
 __device__ __forceinline__ float mlp16_fp32_nt(const float *__restrict__ s, int in0, int nh_rt, float fr, float x,
-                                               float y, float z) {
+                                               float y, float z, uint32_t (*mk)[2] = nullptr) {
     const int nh = NH > 0 ? NH : nh_rt;
     auto relu = [](float v) { return CL ? __builtin_amdgcn_fmed3f(v, 0.0f, 1.0f) : fmaxf(v, 0.0f); };
+    auto mark = [](uint32_t m, float act, int pos) { return (min(__float_as_uint(act), 1u) << pos) | m; };
     // fr: this lane's 4th input (the frame number when rendering; used iff in0 == 4)
     const int lane = lane_id(), g = lane >> 4;
     float a[NT][8];
@@ -158,7 +163,10 @@ __device__ __forceinline__ float mlp16_fp32_nt(const float *__restrict__ s, int 
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) a[t][4 * mt + r] = relu(__builtin_fmaf(c[t][mt][r], s0, bias[4 * mt + r]));
+                for (int r = 0; r < 4; ++r) {
+                    a[t][4 * mt + r] = relu(__builtin_fmaf(c[t][mt][r], s0, bias[4 * mt + r]));
+                    if constexpr (MK) mk[t][0] = mark(mk[t][0], a[t][4 * mt + r], 4 * mt + r);
+                }
     }
     // hidden 32x32 layers: 8 k-steps x 2 row tiles of v_mfma_f32_16x16x4_f32 per point tile
     constexpr bool STREAM = NT <= 2 && CL && NH == 7 && PART == 0;
@@ -190,6 +198,16 @@ __device__ __forceinline__ float mlp16_fp32_nt(const float *__restrict__ s, int 
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) a[t][4 * mt + r] = relu(c[t][mt][r] + bias[4 * mt + r]);
+        if constexpr (MK) {
+            const int pos = 8 * ((jl + 1) & 3);
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    if (jl + 1 < 4) mk[t][0] = mark(mk[t][0], a[t][k], pos + k);
+                    else mk[t][1] = mark(mk[t][1], a[t][k], pos + k);
+                }
+        }
     }
     if constexpr (PART != 0) return a[0][0] + a[NT - 1][7];
     if constexpr (NT >= 3) {

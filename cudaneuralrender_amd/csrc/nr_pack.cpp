@@ -250,6 +250,35 @@ bool pack_fp32_16(const std::vector<int> &dims, const std::vector<std::vector<fl
     return true;
 }
 
+// The backward pack (nr_internal.h): the Keras kernels transposed into A operands.  Raw weights:
+// the gradient's chains are specified on them (include/neural_render.h, nr_mlp_gradient).
+bool pack_grad_16(const std::vector<int> &dims, const std::vector<std::vector<float>> &K, std::vector<float> &pack) {
+    if (!fused_shape_ok(dims)) return false;
+    const int nl = (int)dims.size() - 1, nh = nl - 2, in0 = dims[0];
+    if (nh > GRAD_MAX_HIDDEN) return false;
+    pack.assign(gb_floats(nh), 0.0f);
+    for (int j = 0; j < nh; ++j) {
+        const std::vector<float> &Kj = K[j + 1];
+        for (int st = 0; st < 8; ++st)
+            for (int mt = 0; mt < 2; ++mt) {
+                const int m = 2 * st + mt;
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int i = lane & 15, kk = lane >> 4;
+                    const int uin = 16 * mt + 4 * (i & 3) + (i >> 2), uout = 4 * st + kk;
+                    pack[j * 1024 + ((m >> 2) * 64 + lane) * 4 + (m & 3)] = Kj[(size_t)uin * 32 + uout];
+                }
+            }
+    }
+    for (int st = 0; st < 8; ++st)
+        for (int lane = 0; lane < 64; ++lane) {
+            const int c = lane & 3, kk = lane >> 4;
+            pack[gb_l0(nh) + ((st >> 2) * 64 + lane) * 4 + (st & 3)] = c < in0 ? K[0][(size_t)c * 32 + 4 * st + kk] : 0.0f;
+        }
+    for (int g = 0; g < 4; ++g)
+        for (int k = 0; k < 8; ++k) pack[gb_last(nh) + g * 8 + k] = K[nl - 1][4 * k + g];
+    return true;
+}
+
 bool pack_lowp_32(const std::vector<int> &dims, const std::vector<std::vector<float>> &Kin,
                   const std::vector<std::vector<float>> &Bin, int precision, std::vector<uint16_t> &a_ops,
                   std::vector<float> &fl, int *clamp) {

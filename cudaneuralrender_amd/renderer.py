@@ -511,6 +511,38 @@ class Renderer:
     def mlp_forward_device(self, x_ptr, y_ptr, n):
         self._chk(self._L.nr_mlp_forward(self._ctx, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), n, NR_DEVICE))
 
+    def mlp_gradient(self, X, value=True, grad=True, normal=False, with_stats=False):
+        """nr_mlp_gradient on a host array X [n, dims[0]]: the network's value [n] (nr_mlp_forward's
+        fp32 bits), its exact gradient [n, dims[0]] by one backward pass and the normalised gradient
+        [n, 3] of the first three inputs.  Returns a dict of the numpy arrays asked for ("value",
+        "grad", "normal"; at least one).  Always the fp32 MLP."""
+        X = np.ascontiguousarray(X, np.float32)
+        if X.ndim != 2:
+            raise ValueError(f"X must be [n, inputs], got {X.shape}")
+        n, in0 = X.shape
+        out = {}
+        if value:
+            out["value"] = np.zeros((n,), np.float32)
+        if grad:
+            out["grad"] = np.zeros((n, in0), np.float32)
+        if normal:
+            out["normal"] = np.zeros((n, 3), np.float32)
+        ptr = [out[k].ctypes.data if k in out else None for k in ("value", "grad", "normal")]
+        st = NRStats()
+        self._chk(self._L.nr_mlp_gradient(self._ctx, X.ctypes.data, n, *ptr, NR_HOST,
+                                          ctypes.byref(st) if with_stats else None))
+        return (out, st.as_dict()) if with_stats else out
+
+    def mlp_gradient_device(self, x_ptr, n, value_ptr=None, grad_ptr=None, normal_ptr=None, with_stats=False):
+        """nr_mlp_gradient on device buffers (e.g. torch tensors' data_ptr(): float32 X [n, dims[0]],
+        value [n], grad [n, dims[0]], normal [n, 3]); None = that output is not wanted.  Runs on the
+        context's stream (set_stream) and, without stats, returns without waiting."""
+        vp = [ctypes.c_void_p(p) if p else None for p in (x_ptr, value_ptr, grad_ptr, normal_ptr)]
+        st = NRStats()
+        self._chk(self._L.nr_mlp_gradient(self._ctx, vp[0], int(n), *vp[1:], NR_DEVICE,
+                                          ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
     def layer_forward(self, layer, A):
         A = np.ascontiguousarray(A, np.float32)
         info = self.mlp_info()

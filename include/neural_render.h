@@ -325,6 +325,39 @@ int nr_group_layout(int W, int H, int band, int n, int nframes, size_t *shard_px
 /* Replaces NeuralNetwork::forward(X) (neuralNetwork.cpp:54-63) on a batch:
  * X [n][dims[0]] fp32, Y [n][dims[nlayers]] fp32.  loc = NR_HOST or NR_DEVICE. */
 int nr_mlp_forward(nr_ctx *ctx, const float *X, float *Y, long n, int loc);
+
+/* The network's analytic gradient (a new symbol only: NR_ABI_VERSION stays 3): per point of
+ * X [n][dims[0]] the value, the exact gradient d value / d input by one backward pass, and the
+ * normalised gradient.  One launch; networks of the fused shape [3|4, 32, ..., 32, 1] with at most
+ * 7 hidden 32 x 32 layers (the ReLU masks of the 8 layers are held in registers).
+ *  - Forward: nr_mlp_forward's fp32 pass.  value[i] has the bits nr_mlp_forward gives in fp32;
+ *    nr_set_precision is ignored, as for the ray queries.  X has 3 or 4 columns as the network has:
+ *    a 4-input network takes its 4th input from X, not from the context's frame.
+ *  - Mask: hidden layer l (l = 0 .. nh, the layers with ReLU) has the pre-activation z_l, bias
+ *    added, as the forward computes it; m_l[u] = z_l[u] > 0 (false at 0, false for NaN).
+ *  - Backward, all fp32; every dot product is one fmaf chain from +0.0 over the summed index in
+ *    ascending natural unit order.  With the Keras kernels K_l (in x out):
+ *      g[u] = m_nh[u] ? K_last[u][0] : +0.0;
+ *      for l = nh .. 1: acc[i] = chain over j = 0..31 of fmaf(K_l[i][j], g[j], acc),
+ *                       g[i] = m_(l-1)[i] ? acc[i] : +0.0;
+ *      grad[c] = chain over j of fmaf(K_0[c][j], g[j], +0.0) for c < dims[0].
+ *    (A masked unit contributes an exact +0 operand: masking before the product and skipping the
+ *    term give the same bits for finite weights.)
+ *  - normal[i] = the device normalize3 of the first three gradient components,
+ *    v * (1 / sqrt((x x + y y) + z z)) without contraction -- the arithmetic of nr_trace_rays'
+ *    normals; a zero gradient gives what that arithmetic gives (NaN).  For NR_SCENE_TANH and
+ *    NR_SCENE_ROUND this is the scene's exact normal direction (tanh and the offset are monotone);
+ *    the other scenes compose spheres and cylinders, whose gradient is not computed here.
+ *  - A point's outputs depend only on that point: the same bits for any n, order or split into calls.
+ *    Non-finite inputs: unspecified outputs, no fault.
+ *  - value [n], grad [n][dims[0]], normal [n][3]: any may be NULL, not all three.  loc = NR_HOST or
+ *    NR_DEVICE for all the pointers.  stats (may be NULL): ray_steps = n, launches, ms_total;
+ *    everything else 0.
+ * Errors: NR_E_INVALID (ctx NULL, n < 0, n > 2^30, X NULL with n > 0, every output NULL),
+ * NR_E_STATE (no network), NR_E_FORMAT (a network the fused kernels do not take, or more than 7
+ * hidden 32 x 32 layers: there is no layered fallback).  n = 0 returns NR_OK without a launch. */
+int nr_mlp_gradient(nr_ctx *ctx, const float *X /*[n][dims[0]]*/, long n, float *value /*[n] or NULL*/,
+                    float *grad /*[n][dims[0]] or NULL*/, float *normal /*[n][3] or NULL*/, int loc, nr_stats *stats);
 /* One DenseLayer::forward (denseLayer.cu:229-278) on device buffers: layer l of the
  * loaded network applied to A [n][dims[l]] -> Z [n][dims[l+1]]. */
 int nr_layer_forward(nr_ctx *ctx, int layer, const float *A, float *Z, long n, int loc);
