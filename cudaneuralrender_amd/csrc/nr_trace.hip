@@ -78,8 +78,9 @@ constexpr int NR_DENSE_GEN = 1;
 constexpr int NR_QUEUE_TWO_RANGES = 1;
 constexpr int NR_QUEUE_CHUNK_DENSE = 64;
 constexpr int NR_QUEUE_CHUNK_DENSE1 = 32;
-// (fp32: A/B only -- its ring would cost the batched instance its fourth workgroup per CU)
-constexpr int NR_DENSE_GEN_FP32 = 0;
+// (the batched fp32 tracer generates in bulk too, with the generated rays in registers -- one spare
+// ray per lane, RREG in k_trace: the LDS ring cost it its fourth workgroup per CU, which was worth as
+// much as the ring, profiles/r3_ab_experiments.txt (14); the one-frame fp32 tracer generates in-lane)
 
 // Refill only once this many ray slots are free (or the wave is empty), so that the ray
 // generation and the queue bookkeeping are paid for several rays at a time: bf16 batch
@@ -87,6 +88,9 @@ constexpr int NR_DENSE_GEN_FP32 = 0;
 // (profiles/r1_ab_experiments.txt).
 constexpr int NR_REFILL_MIN_LOWP = 8;
 constexpr int NR_REFILL_MIN_FP32 = 4;
+// the batched fp32 tracer, which deals a generated ray with nine cross-lane reads: 1 / 2 / 4 ->
+// 1.705 / 1.712 / 1.726 ms/frame (1 and 2 within the runs' spread; profiles/r7_reg_ring.txt)
+constexpr int NR_REFILL_MIN_FP32_BATCH = 2;
 
 typedef __attribute__((address_space(1))) uint32_t *gptr_u32;
 
@@ -253,9 +257,14 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
     constexpr bool QPF = PREC == NR_PRECISION_FP32 ? NR_QUEUE_PREFETCH_FP32 : NR_QUEUE_PREFETCH_LOWP;  // queue pools
     constexpr int NONMLP_PRIO = PREC == NR_PRECISION_FP32 ? NR_NONMLP_PRIO : 0;
     constexpr int MLP_PRIO = PREC == NR_PRECISION_BF16 || PREC == NR_PRECISION_FP16 ? NR_MLP_PRIO_LOWP : 0;
-    constexpr int RMIN = PREC == NR_PRECISION_FP32 ? NR_REFILL_MIN_FP32 : NR_REFILL_MIN_LOWP;  // free slots per refill
     // rays generated in bulk through an LDS buffer (NR_DENSE_GEN): the reduced-precision tracers
-    constexpr bool DENSE = NR_DENSE_GEN && (PREC != NR_PRECISION_FP32 || NR_DENSE_GEN_FP32) && !PROBE;
+    constexpr bool DENSE = NR_DENSE_GEN && PREC != NR_PRECISION_FP32 && !PROBE;
+    // rays generated in bulk into registers, one spare ray per lane: the batched fp32 tracer, whose
+    // 4 workgroups per CU leave no LDS for a ring
+    constexpr bool RREG = PREC == NR_PRECISION_FP32 && BATCH && !PROBE && !STAMPS;
+    constexpr int RMIN = RREG ? NR_REFILL_MIN_FP32_BATCH
+                         : PREC == NR_PRECISION_FP32 ? NR_REFILL_MIN_FP32 : NR_REFILL_MIN_LOWP;  // free slots per refill
+    constexpr bool RING = DENSE || RREG;  // the wave holds generated rays (rb_n of them) besides its marching ones
     constexpr bool TWO = DENSE && NR_QUEUE_TWO_RANGES;
     // pool size; the next reservation is requested when the pool holds fewer than QLOW
     const uint32_t QCHUNK = TWO ? (BATCH && T.nframes >= 4 ? NR_QUEUE_CHUNK_DENSE : NR_QUEUE_CHUNK_DENSE1) : NR_QUEUE_CHUNK;
@@ -284,9 +293,8 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
     __shared__ uint8_t stash_f[NW][BATCH ? STASH : 1];
     // DENSE: per wave a ring of RB generated rays {p.xyz, tfar}, {d.xyz, pixel} (+ frame), as two
     // arrays of 16-byte entries so that consecutive lanes' ds_write_b128 / ds_read_b128 stay
-    // conflict-free: 64 rays, 8.25 KB per workgroup (the fp32 tracer's ring, an A/B build option,
-    // holds 16: its 4 workgroups per CU have 2 KB of LDS left each)
-    constexpr int RB = PREC == NR_PRECISION_FP32 ? 16 : NR_RING_LOWP;
+    // conflict-free: 64 rays, 8.25 KB per workgroup
+    constexpr int RB = NR_RING_LOWP;
     __shared__ float4 rbuf_p[DENSE ? NW : 1][DENSE ? RB : 1], rbuf_d[DENSE ? NW : 1][DENSE ? RB : 1];
     __shared__ uint8_t rbuf_f[DENSE && BATCH ? NW : 1][DENSE && BATCH ? RB : 1];
     // each lane's marching ray {d.xyz, pixel} (DLDS): 4 KB per workgroup
@@ -324,6 +332,11 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
     uint32_t pool_base = 0, pool_cnt = 0, pend_v = 0;  // NR_QUEUE_PREFETCH state
     bool pend = false;
     uint32_t rb_n = 0, rb_head = 0;  // DENSE: rays in the wave's buffer, ring position of the first
+    // RREG: the wave's generated rays not yet dealt are the spares of lanes [rb_head, rb_head + rb_n)
+    F3 sp_p = mk3(0, 0, 0), sp_d = mk3(0, 0, 0);
+    float sp_tfar = 0.0f;
+    uint32_t sp_pix = 0;
+    int sp_f = 0;
     F3 p = mk3(0, 0, 0), d = mk3(0, 0, 0);
     float tfar = 0.0f;
     uint32_t pix = 0;
@@ -360,7 +373,7 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
         if constexpr (EG) nfq = __builtin_amdgcn_readfirstlane(nfq);
         NR_PHASE(refill);
         // ---- refill free slots from the pixel queue
-        if (!qempty || (DENSE && rb_n > 0)) {
+        if (!qempty || (RING && rb_n > 0)) {
 #if NR_ARG_RELOAD
             const TraceKargs *K = fresh_kargs();
             const RenderArgs &A = K->A;
@@ -377,7 +390,7 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
             const uint64_t freem = __ballot(it < 0) & T.lane_cap;
             const uint32_t nfree = (uint32_t)__popcll(freem);
             // (a drained queue's buffered rays are dealt at once: they are the frame's last)
-            if (nfree >= (uint32_t)RMIN || (nfree && nfree == (uint32_t)T.take) || (DENSE && qempty && nfree)) {
+            if (nfree >= (uint32_t)RMIN || (nfree && nfree == (uint32_t)T.take) || (RING && qempty && nfree)) {
                 auto shard_total = [&](int sh) -> long {
                     const long sh_chunks = sh < nchunks ? ((nchunks - 1 - sh) >> T.nq_shift) + 1 : 0;
                     return (PROBE ? sh_chunks : sh_chunks * 64) * (BATCH ? T.nframes : 1);
@@ -590,6 +603,74 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
                             ph[7] += __builtin_amdgcn_s_memtime() - tsub;
                         }
                     }
+                } else if constexpr (RREG) {
+                    // Bulk generation without LDS: every lane generates the ray of one reserved
+                    // position (up to min(take, 64) of them), background pixels are written at
+                    // once, and the hits are moved to the lowest lanes (ds_permute: cross-lane, no
+                    // LDS memory) as those lanes' spare rays.  The free slot of rank r among the
+                    // free slots then takes the spare of lane rb_head + r (ds_bpermute).  The
+                    // spares left are dealt before the next generation overwrites them; a
+                    // generation that yields fewer hits than there are free slots is followed by
+                    // another.
+                    auto xl_push = [](int addr, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)v); };
+                    auto xl_pull = [](int addr, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)v); };
+                    auto xl_pushf = [&](int addr, float v) { return __uint_as_float(xl_push(addr, __float_as_uint(v))); };
+                    auto xl_pullf = [&](int addr, float v) { return __uint_as_float(xl_pull(addr, __float_as_uint(v))); };
+                    while (true) {
+                        const uint64_t fm = __ballot(it < 0) & T.lane_cap;
+                        const uint32_t nf = (uint32_t)__popcll(fm);
+                        const uint32_t take = min(nf, rb_n);
+                        if (take) {
+                            const uint32_t rank = rank_below(fm);
+                            const int src = (int)(((rb_head + rank) & 63u) << 2);
+                            const F3 np = mk3(xl_pullf(src, sp_p.x), xl_pullf(src, sp_p.y), xl_pullf(src, sp_p.z));
+                            const F3 nd = mk3(xl_pullf(src, sp_d.x), xl_pullf(src, sp_d.y), xl_pullf(src, sp_d.z));
+                            const float nt = xl_pullf(src, sp_tfar);
+                            const uint32_t npix = xl_pull(src, sp_pix);
+                            const int nfr = (int)xl_pull(src, (uint32_t)sp_f);
+                            if (it < 0 && rank < take) {
+                                p = np;
+                                d = nd;
+                                tfar = nt;
+                                pix = npix;
+                                rf = nfr;
+                                it = 0;
+                            }
+                            rb_head += take;
+                            rb_n -= take;
+                        }
+                        if (take == nf || qempty) break;
+                        // free slots remain and no spare is left
+                        uint32_t base = 0, got = 0;
+                        reserve((uint32_t)min(T.take, 64), base, got);
+                        if (!got) continue;  // (the queue is drained)
+                        bool hit = false, keep = false;
+                        F3 gp = mk3(0.0f, 0.0f, 0.0f), gd = mk3(0.0f, 0.0f, 0.0f);
+                        float gt = 0.0f;
+                        uint32_t glp = 0;
+                        int gf = 0;
+                        if ((uint32_t)lane < got) {
+                            int px, py;
+                            if (pixel_of(base + (uint32_t)lane, gf, px, py)) {
+                                glp = (uint32_t)((long)py * A.W + px);
+                                hit = gen_ray(A, T, sf[gf].inv_view, px, py, gp, gd, gt);
+                                keep = hit && A.max_steps > 0;
+                                if (!keep) put(gf, glp, 0u);  // background (:335-339) or no iterations at all
+                            }
+                        }
+                        nhit += (uint32_t)__popcll(__ballot(hit));
+                        const uint64_t km = __ballot(keep);
+                        const uint32_t nk = (uint32_t)__popcll(km);
+                        // a permutation of the lanes: the kept rays to lanes [0, nk) in order, the rest behind them
+                        const int dst = (int)((keep ? rank_below(km) : nk + rank_below(~km)) << 2);
+                        sp_p = mk3(xl_pushf(dst, gp.x), xl_pushf(dst, gp.y), xl_pushf(dst, gp.z));
+                        sp_d = mk3(xl_pushf(dst, gd.x), xl_pushf(dst, gd.y), xl_pushf(dst, gd.z));
+                        sp_tfar = xl_pushf(dst, gt);
+                        sp_pix = xl_push(dst, glp);
+                        sp_f = (int)xl_push(dst, (uint32_t)gf);
+                        rb_head = 0;
+                        rb_n = nk;
+                    }
                 } else {
                     uint32_t base = 0, got = 0;
                     reserve(nfree, base, got);
@@ -616,7 +697,7 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
             }
         }
         // the queue drained and no ray left to deal: the tail of the launch
-        const bool drained = qempty && (!DENSE || rb_n == 0);
+        const bool drained = qempty && (!RING || rb_n == 0);
         NR_PHASE(shading);
         // ---- colour stashed converged rays: 16 rays x 4 tetrahedron samples per pass.
         // Once the queue is drained a partial pass waits until the wave's last ray has
