@@ -129,8 +129,9 @@ bool pack_lowp_32(const std::vector<int> &dims, const std::vector<std::vector<fl
 // layer unchanged.  Same sizes as the 32x32x16 pack.
 void pack_lowp_s16(const std::vector<uint16_t> &a32, const std::vector<float> &f32, int nh,
                    std::vector<uint16_t> &a16, std::vector<float> &f16);
-// ok (if not null) = 1 when the scales exist (every scaled weight and bound inside fp16's range);
-// otherwise the kernels run the fp32 MLP for every point
+// ok (if not null) = 1 when the scales exist (every scaled weight and bound inside fp16's range)
+// and leave every ReLU layer's activations inside the window where the split keeps its bits
+// (nr_pack.cpp X3_SPLIT_FLOOR); otherwise the kernels run the fp32 MLP for every point
 bool pack_x3_32(const std::vector<int> &dims, const std::vector<std::vector<float>> &kernels,
                 const std::vector<std::vector<float>> &biases, std::vector<uint16_t> &a_ops, std::vector<float> &fl,
                 int *ok = nullptr);

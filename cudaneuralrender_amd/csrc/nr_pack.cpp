@@ -167,6 +167,42 @@ static bool box_tops(const std::vector<int> &dims, const std::vector<std::vector
     return ok;
 }
 
+// What the network does, against what box_tops proves: every ReLU layer's largest activation over
+// a fixed set of X3_PROBE_POINTS points of the +-1.2 box the tracers march in (a 4th input, the
+// frame number, in [0, 360)), in double over the exact f32 weights.  The points come from a
+// fixed-seed splitmix64 sequence, so the result is a function of the network alone.
+constexpr int X3_PROBE_POINTS = 2048;
+// the lowest binade whose fp16 hi + residual split keeps 22 bits: 11 + 11 - 1 bits above 2^-24
+constexpr int X3_SPLIT_FLOOR = -24 + 21;
+static void sampled_tops(const std::vector<int> &dims, const std::vector<std::vector<float>> &K,
+                         const std::vector<std::vector<float>> &B, std::vector<double> &seen) {
+    const int nl = (int)dims.size() - 1, in0 = dims[0];
+    uint64_t s = 0x6e72783364657074ull;
+    auto unit = [&s]() {  // splitmix64 -> [0, 1)
+        uint64_t z = (s += 0x9e3779b97f4a7c15ull);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        return (double)((z ^ (z >> 31)) >> 11) * 0x1p-53;
+    };
+    seen.assign(nl - 1, 0.0);
+    std::vector<double> a, n;
+    for (int p = 0; p < X3_PROBE_POINTS; ++p) {
+        a.assign(in0, 0.0);
+        for (int i = 0; i < in0; ++i) a[i] = i < 3 ? -1.2 + 2.4 * unit() : 360.0 * unit();
+        for (int l = 0; l < nl - 1; ++l) {
+            const int in = dims[l], out = dims[l + 1];
+            n.assign(out, 0.0);
+            for (int u = 0; u < out; ++u) {
+                double v = B[l][u];
+                for (int i = 0; i < in; ++i) v += (double)K[l][(size_t)i * out + u] * a[i];
+                n[u] = std::max(v, 0.0);
+                seen[l] = std::max(seen[l], n[u]);
+            }
+            a.swap(n);
+        }
+    }
+}
+
 // Layer l's weights times 2^(e[l-1] - e[l]) and its bias times 2^-e[l] (e[-1] = 0, e[last]
 // = 0): activations come out scaled by 2^-e[l] and the last layer's output unscaled.
 static void apply_scales(const std::vector<int> &e, std::vector<std::vector<float>> &K,
@@ -397,7 +433,9 @@ void pack_lowp_s16(const std::vector<uint16_t> &a32, const std::vector<float> &f
 // 2^(-e[0] - X3_XYZ_SHIFT) (the kernel scales the inputs by 2^X3_XYZ_SHIFT), its 4th-input
 // weights by 2^-e[0]; the final layer keeps f32 weights times 2^e[last].  Every scaling is by a
 // power of two, so the split approximates the unscaled network; the fp16 range limits it
-// (hi below 2^15), otherwise ok = 0 and the kernels run the fp32 MLP.
+// (hi below 2^15), and so does the slack of the bounds (a layer whose activations over the probe
+// points all sit below the window in which the split keeps its 22 bits, below); otherwise ok = 0
+// and the kernels run the fp32 MLP.
 bool pack_x3_32(const std::vector<int> &dims, const std::vector<std::vector<float>> &K,
                 const std::vector<std::vector<float>> &B, std::vector<uint16_t> &a_ops, std::vector<float> &fl,
                 int *ok_out) {
@@ -419,6 +457,20 @@ bool pack_x3_32(const std::vector<int> &dims, const std::vector<std::vector<floa
             e[l] = top[l] > 0.0 ? (int)std::ceil(std::log2(top[l])) - 10 : 0;
             if (e[l] < -100 || e[l] > 100) ok = false;
         }
+    }
+    if (ok) {
+        // The interval bounds are hard but not tight, and their slack compounds with depth: the
+        // scaled activations then sit far below the 2^10 the scales aim at.  A scaled one in [2^E,
+        // 2^(E+1)) splits into ah = rtz_f16(a), 11 bits from 2^E down, and a residual below
+        // 2^(E-10) whose 11 bits reach down to 2^(E-21); fp16's smallest subnormal is 2^-24, so
+        // the split holds all 22 bits only for E >= -3.  A layer whose largest activation over
+        // the probe points (sampled_tops) is below 2^-3 scaled has lost bits in every unit: the
+        // pack is refused (the kernels then run the fp32 MLP).  A layer that is zero at every probe
+        // point has nothing to lose.  DESIGN.md section 2, "fp32x3: when the pack is refused".
+        std::vector<double> seen;
+        sampled_tops(dims, K, B, seen);
+        for (int l = 0; l < nl - 1; ++l)
+            if (seen[l] > 0.0 && seen[l] < std::ldexp(1.0, e[l] + X3_SPLIT_FLOOR)) ok = false;
     }
     const int ex = X3_XYZ_SHIFT;
     // fp16 hi / residual of a scaled weight; every hi must stay below 2^15

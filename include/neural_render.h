@@ -45,7 +45,12 @@ extern "C" {
 #define NR_PRECISION_FP32X3 3 /* fp32-class on the fp16 matrix core: three-term split a.w ~ ah.wh + al.wh + ah.wl,
                                   f32 accumulate (~2-3x the f32 chain's error against an exact
                                   evaluation); normals evaluated in fp32 (bit-exact); points with
-                                  inputs outside the pack's bounds run the fp32 MLP */
+                                  inputs outside the pack's bounds run the fp32 MLP.  A network whose
+                                  pack is refused (nr_pack_x3 *ok = 0: scales outside fp16's range, or
+                                  interval bounds so far above the network's activations that the
+                                  split would lose bits -- dense networks of more than ~8 hidden
+                                  layers) runs the fp32 MLP at every point,
+                                  bit-exact with NR_PRECISION_FP32 */
 
 /* scene composition, sceneSDF (volumeRender_kernel.cu:217-230) */
 #define NR_SCENE_V1 0        /* v1: manySphere(p, nSDF, true) -- 9-sphere smooth union (:222) */
@@ -112,7 +117,8 @@ int nr_load_mlp(nr_ctx *ctx, int nlayers, const int *dims,
                 const float *const *kernels, const float *const *biases);
 /* The fp32x3 pack of a [3|4, 32, ..., 32, 1] network (host only, no GPU): fp16 hi / residual
  * operands a[*a_len] in the kernels' layout and the floats f[*f_len] (scaled biases, final layer,
- * scales); *ok = 0 when the scales do not fit fp16 (the kernels then run fp32).  Copies only when
+ * scales); *ok = 0 when the scales do not fit fp16 or leave the activations below the window in
+ * which the fp16 split keeps its bits (the kernels then run fp32).  Copies only when
  * the capacities suffice (call with a = f = NULL for the lengths).  For the test oracle's fp32x3
  * emulation (the bf16/fp16 tracers' normals); not part of the reference's interface. */
 int nr_pack_x3(int nlayers, const int *dims, const float *const *kernels, const float *const *biases,
@@ -420,8 +426,10 @@ int nr_set_debug(nr_ctx *ctx, int flags);
  * takes every later step of its march in fp32x3, so the convergence test (tstep < 1e-6,
  * volumeRender_kernel.cu:474), the background test and the hit point are decided at fp32-class
  * precision while the bulk of the march stays 16-bit.  Default NR_ENDGAME_DEFAULT; 0 = the pure
- * 16-bit march.  It needs the network's fp32x3 pack (the 7-hidden-layer [3|4, 32..., 1] shape whose
- * scales fit, as for the fp32x3 normals) and is off with nr_set_debug bit 15 (fp32 normals); the
+ * 16-bit march.  It needs the network's fp32x3 pack (a [3|4, 32..., 1] network whose pack
+ * nr_pack_x3 accepts, as for the fp32x3 normals): a network whose pack is refused marches in pure
+ * 16 bits whatever tau is, takes its normals from the fp32 MLP and reports endgame_evals = 0.  It
+ * is off with nr_set_debug bit 15 (fp32 normals) too; the
  * wavefront schedule applies it too (round 6: a fine queue per iteration, the same frames), the
  * layered schedule renders fp32.  nr_stats.endgame_evals counts the fp32x3
  * evaluations, nr_stats.endgame_switches the rays handed over.  The default (round 6, DESIGN.md
