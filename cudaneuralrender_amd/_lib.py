@@ -38,6 +38,7 @@ EXPORTS = [
     "nr_trace_rays", "nr_render_gbuffer",
     "nr_sample_grid", "nr_mesh_grid", "nr_extract_mesh", "nr_obj_save",
     "nr_mlp_gradient",
+    "nr_pack_fp32_pruned", "nr_set_prune", "nr_prune_info", "nr_prune_redos",
 ]
 
 
@@ -165,6 +166,11 @@ def lib():
         "nr_set_schedule": (I, [P, I]),
         "nr_set_debug": (I, [P, I]),
         "nr_set_endgame": (I, [P, F]),
+        "nr_pack_fp32_pruned": (I, [I, IP, ctypes.POINTER(FP), ctypes.POINTER(FP), I, FP, FP, ctypes.c_long,
+                                    ctypes.POINTER(ctypes.c_long), IP, IP, IP, IP, IP, I]),
+        "nr_set_prune": (I, [P, I]),
+        "nr_prune_info": (I, [P, IP, IP, IP, IP, I]),
+        "nr_prune_redos": (I, [P, ctypes.POINTER(ctypes.c_ulonglong)]),
         "nr_set_occupancy": (I, [P, I]),
         "nr_set_pixel_spread": (I, [P, I]),
         "nr_set_cost_probe": (I, [P, I, I]),

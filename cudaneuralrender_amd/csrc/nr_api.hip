@@ -60,6 +60,9 @@ struct nr_ctx {
     bool no_clamp = false;  // nr_set_debug bit 9: bf16 ReLU by v_pk_max_i16, fp32 by add + max,
                             // on the same packs
     bool f32_clamp_ok = false;  // the fp32 pack is scaled for the clamped ReLU (pack_fp32_16)
+    float *d_pkp = nullptr;     // the pruned fp32 pack (pack_fp32_16_pruned; the batched fp32 k_trace), null: none
+    PruneInfo prune;            // its order and k-steps (nrelu = 0: none)
+    int prune_mode = 1;         // nr_set_prune
     int schedule = 0; // NR_SCHED_PERSISTENT
     uint32_t *d_tr = nullptr;  // persistent-schedule counters + stats
     int debug = 0;
@@ -195,7 +198,7 @@ int free_network(nr_ctx *c) {
     for (auto *p : c->d_W) (void)hipFree(p);
     for (auto *p : c->d_b) (void)hipFree(p);
     c->d_W.clear(); c->d_b.clear();
-    dfree(c->d_pack16); dfree(c->d_gpack16); dfree(c->d_lp16); dfree(c->d_lpf16); dfree(c->d_x3lp); dfree(c->d_x3fl);
+    dfree(c->d_pack16); dfree(c->d_pkp); dfree(c->d_gpack16); dfree(c->d_lp16); dfree(c->d_lpf16); dfree(c->d_x3lp); dfree(c->d_x3fl);
     dfree(c->d_lps16); dfree(c->d_lpfs16);
     c->fused = false;
     if (c->lgraph) { (void)hipGraphExecDestroy(c->lgraph); c->lgraph = nullptr; }
@@ -274,6 +277,27 @@ int upload_lowp(nr_ctx *c) {
     return NR_OK;
 }
 
+// The pruned fp32 pack for c->prune_mode beside the full one (same size); MlpArgs::pkp only while
+// the clamped form is on (nr_set_debug bit 9 turns both off).
+int upload_pruned(nr_ctx *c) {
+    dfree(c->d_pkp);
+    c->prune = PruneInfo{};
+    c->mlp16.pkp = nullptr;
+    c->mlp16.ks_bits = 0;
+    if (!c->fused) return NR_OK;
+    std::vector<float> pp;
+    if (!pack_fp32_16_pruned(c->dims, c->kernels, c->biases, c->prune_mode, pp, c->prune)) {
+        c->prune = PruneInfo{};
+        return NR_OK;
+    }
+    pp.resize((size_t)c->mlp16.pk_bytes / 4, 0.0f);
+    HIPCHK(c, hipMalloc(&c->d_pkp, (size_t)c->mlp16.pk_bytes));
+    HIPCHK(c, hipMemcpy(c->d_pkp, pp.data(), (size_t)c->mlp16.pk_bytes, hipMemcpyHostToDevice));
+    c->mlp16.ks_bits = prune_ks_bits(c->prune);
+    c->mlp16.pkp = c->mlp16.f32_clamp ? c->d_pkp : nullptr;
+    return NR_OK;
+}
+
 int set_network(nr_ctx *c, std::vector<int> dims, std::vector<std::vector<float>> K, std::vector<std::vector<float>> B) {
     HIPCHK(c, hipSetDevice(c->device));
     free_network(c);
@@ -318,6 +342,8 @@ int set_network(nr_ctx *c, std::vector<int> dims, std::vector<std::vector<float>
             HIPCHK(c, hipMemcpy(c->d_gpack16, gpack.data(), gb, hipMemcpyHostToDevice));
             c->gpack_bytes = (int)gb;
         }
+        int rc;
+        if ((rc = upload_pruned(c)) != NR_OK) return rc;
     }
     return upload_lowp(c);
 }
@@ -1672,6 +1698,37 @@ int nr_pack_x3(int nlayers, const int *dims, const float *const *kernels, const 
     return NR_OK;
 }
 
+int nr_pack_fp32_pruned(int nlayers, const int *dims, const float *const *kernels, const float *const *biases, int mode,
+                        float *full, float *pruned, long cap, long *len, int *clamp, int *has_pruned, int *cand,
+                        int *ks, int *order, int cap_layers) {
+    if (nlayers < 1 || !dims || !kernels || !biases || !len || !clamp || !has_pruned || mode < 0 || mode > 2)
+        return nr::report_error(NR_E_INVALID, "nr_pack_fp32_pruned: bad arguments");
+    std::vector<int> d(dims, dims + nlayers + 1);
+    std::vector<std::vector<float>> K(nlayers), B(nlayers);
+    for (int l = 0; l < nlayers; ++l) {
+        if (!kernels[l] || !biases[l] || d[l] < 1 || d[l + 1] < 1)
+            return nr::report_error(NR_E_INVALID, "nr_pack_fp32_pruned: layer %d", l);
+        K[l].assign(kernels[l], kernels[l] + (size_t)d[l] * d[l + 1]);
+        B[l].assign(biases[l], biases[l] + d[l + 1]);
+    }
+    std::vector<float> fv, pv;
+    int cl = 0;
+    if (!pack_fp32_16(d, K, B, fv, &cl)) return nr::report_error(NR_E_INVALID, "nr_pack_fp32_pruned: not a fused shape");
+    PruneInfo P;
+    const bool hp = pack_fp32_16_pruned(d, K, B, mode, pv, P);
+    *len = (long)fv.size();
+    *clamp = cl;
+    *has_pruned = hp ? 1 : 0;
+    if (full && cap >= (long)fv.size()) std::memcpy(full, fv.data(), fv.size() * 4);
+    if (hp && pruned && cap >= (long)pv.size()) std::memcpy(pruned, pv.data(), pv.size() * 4);
+    if (hp && cap_layers >= P.nrelu) {
+        if (cand) std::copy(P.cand.begin(), P.cand.end(), cand);
+        if (ks) std::copy(P.ks.begin(), P.ks.end(), ks);
+        if (order) std::copy(P.order.begin(), P.order.end(), order);
+    }
+    return NR_OK;
+}
+
 int nr_mlp_forward(nr_ctx *c, const float *X, float *Y, long n, int loc) {
     if (!c || (n > 0 && (!X || !Y)) || n < 0) return set_err(c, NR_E_INVALID, "nr_mlp_forward: bad arguments");
     if (c->dims.empty()) return set_err(c, NR_E_STATE, "nr_mlp_forward: no network loaded");
@@ -1928,6 +1985,45 @@ int nr_set_debug(nr_ctx *c, int flags) {
     c->mlp16.lp_stream = !c->no_stream;
     c->mlp16.lp_clamp = c->clamp_ok && !c->no_clamp && c->mlp16.lp != nullptr;
     c->mlp16.f32_clamp = c->f32_clamp_ok && !c->no_clamp;
+    c->mlp16.pkp = c->mlp16.f32_clamp ? c->d_pkp : nullptr;
+    return NR_OK;
+}
+
+int nr_set_prune(nr_ctx *c, int mode) {
+    if (!c) return set_err(nullptr, NR_E_INVALID, "ctx is NULL");
+    if (mode < 0 || mode > 2) return set_err(c, NR_E_INVALID, "nr_set_prune: mode must be 0, 1 or 2");
+    if (mode == c->prune_mode) return NR_OK;
+    c->prune_mode = mode;
+    if (c->dims.empty()) return NR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    {
+        GET_STREAM(c, s_);
+        HIPCHK(c, hipStreamSynchronize(s_));
+    }
+    return upload_pruned(c);
+}
+
+int nr_prune_info(const nr_ctx *c, int *nrelu, int *cand, int *ks, int *order, int cap_layers) {
+    if (!c || !nrelu) return set_err(nullptr, NR_E_INVALID, "nr_prune_info: NULL argument");
+    const PruneInfo &P = c->prune;
+    *nrelu = P.nrelu;
+    if (cap_layers >= P.nrelu) {
+        if (cand) std::copy(P.cand.begin(), P.cand.end(), cand);
+        if (ks) std::copy(P.ks.begin(), P.ks.end(), ks);
+        if (order) std::copy(P.order.begin(), P.order.end(), order);
+    }
+    return NR_OK;
+}
+
+int nr_prune_redos(nr_ctx *c, unsigned long long *redos) {
+    if (!c || !redos) return set_err(c, NR_E_INVALID, "nr_prune_redos: NULL argument");
+    *redos = 0;
+    if (!c->d_tr) return NR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipMemcpy(redos, reinterpret_cast<unsigned long long *>(c->d_tr + NR_MAX_QUEUES * 32) + 6, 8,
+                        hipMemcpyDeviceToHost));
     return NR_OK;
 }
 

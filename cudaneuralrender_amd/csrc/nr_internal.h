@@ -115,6 +115,37 @@ bool fused_shape_ok(const std::vector<int> &dims);
 // pack_fp32_16: clamp (if not null) = 1 when the pack is scaled for the clamped ReLU
 bool pack_fp32_16(const std::vector<int> &dims, const std::vector<std::vector<float>> &kernels,
                   const std::vector<std::vector<float>> &biases, std::vector<float> &pack, int *clamp = nullptr);
+// The pruned fp32 pack (the batched fp32 k_trace; nr_mlp16.h mlp16_fp32_pruned): the scaled pack's
+// values in the PK_* layout, except that
+//   * the units of every ReLU layer l (0..nh) are re-ordered: position p holds unit order[l][p] --
+//     the layer's live units in ascending index, then its cand[l] candidates (a multiple of 4:
+//     units that fire at next to no point of the marched volume).  Rows (outputs, biases) and the
+//     next layer's k positions follow the same order, so a chain over positions 0..31 is the
+//     original chain with the candidates' terms moved to its end, and ks[l] = (32 - cand[l]) / 4
+//     is the number of k-steps the next layer needs while every candidate's activation is +0;
+//   * the last ReLU layer keeps position 4k + g in register k of lane group g like the others
+//     (the full pack: 8g + k), and the final weights are stored by position: the final chain runs
+//     in the point's own lane after a transpose, at every tile count.
+// mode (nr_set_prune): 0 = no candidates (identity order, ks all 8); 1 = candidates chosen from
+// the units' firing counts over a fixed sample (nr_pack.cpp, the rule in DESIGN.md section 5);
+// 2 = the four highest-numbered units of every layer.  No candidates either for 4 inputs,
+// non-finite weights or a bias of -0.  False (no pack) if the shape is not fused or the scaled
+// pack is refused.
+struct PruneInfo {
+    int nrelu = 0;           // ReLU layers: nh + 1
+    std::vector<int> cand;   // [nrelu]
+    std::vector<int> ks;     // [nrelu], 4..8
+    std::vector<int> order;  // [nrelu][32]
+};
+bool pack_fp32_16_pruned(const std::vector<int> &dims, const std::vector<std::vector<float>> &kernels,
+                         const std::vector<std::vector<float>> &biases, int mode, std::vector<float> &pack,
+                         PruneInfo &info);
+// MlpArgs::ks_bits: ks[l] - 4 in bits [3l, 3l + 3)
+inline unsigned long long prune_ks_bits(const PruneInfo &p) {
+    unsigned long long b = 0;
+    for (int l = 0; l < p.nrelu; ++l) b |= (unsigned long long)(p.ks[l] - 4) << (3 * l);
+    return b;
+}
 // the backward pack (above); false if the shape is not fused or has more than GRAD_MAX_HIDDEN
 // hidden 32 x 32 layers
 bool pack_grad_16(const std::vector<int> &dims, const std::vector<std::vector<float>> &kernels,

@@ -43,6 +43,10 @@ struct MlpArgs {
     const float *lpfs;      // (nr_pack.cpp pack_lowp_s16; null: not built, or nr_set_debug bit 12 clear)
     int lp_s16;             // k_mlp16 only (launch_mlp16): lp / lpf ARE the 16x16x32 layout, every
                             // chunk takes the NR_S16_* stream
+    const float *pkp;       // the batched fp32 k_trace: the pruned fp32 pack (nr_internal.h PruneInfo), which
+                            // it stages in LDS instead of pk; null: none (the scaled pack was refused, or
+                            // f32_clamp is off) -- it then stages pk and runs the add + max form
+    unsigned long long ks_bits;  // pkp: k-steps per ReLU layer, ks[l] - 4 in bits [3l, 3l + 3)
 };
 
 // Per-render constants (the reference's __constant__ state, volumeRender_kernel.cu:31-35,
@@ -121,7 +125,8 @@ struct TraceArgs {
     uint32_t *pix_ctr;          // 2^nq_shift pixel-queue shard counters, one per 128-byte line (stride 32)
     int nq_shift;
     unsigned long long *stats;  // [0] ray-steps, [1] rays hit, [2] max iterations, [3] rays shaded,
-                                // [4] fp32x3 march evaluations (the endgame)
+                                // [4] fp32x3 march evaluations (the endgame), [5] rays handed to it,
+                                // [6] wave evaluations redone on the full fp32 pack (MlpArgs::pkp)
     unsigned long long *stamps; // diagnostics (nr_set_debug): per wave {start, queue drained, end, ray-steps}
     // pixel queue over 8x8 pixel blocks of the shard image, dispensed in `order`
     // (NULL = raster order); bcost (may be NULL) receives each block's max ray iterations

@@ -13,6 +13,8 @@
 // runs over k = 0..31 in ascending order from +0, then adds the bias -- bit-for-bit the
 // reference dense layer as restated by the oracle (denseLayer.cu:126-176).
 #pragma once
+#include <type_traits>
+
 #include "nr_device.h"
 #include "nr_mlp16_asm.h"
 
@@ -303,6 +305,195 @@ template <bool ST = false>
 __device__ __forceinline__ float mlp16_fp32(const MlpArgs &M, const float *s, float fr, float x, float y, float z,
                                             uint32_t tmask) {
     return mlp16_fp32<ST>(s, M.in0, M.nh, fr, x, y, z, tmask, M.f32_clamp && inputs_in_bound_f32(x, y, z, fr));
+}
+
+// ---- the clamped fp32 MLP on the pruned pack (nr_internal.h PruneInfo; the batched fp32 k_trace) ----
+//
+// A trained ReLU network has units that fire at next to no point of the marched volume.  The pack
+// puts each layer's candidates behind its live units, so the next layer's chain over positions
+// 0..31 is the original chain (live units ascending) with the candidates' terms at its end, and
+// the last 8 - ks k-steps hold candidates only.  While every candidate's activation is +0 those
+// k-steps are skipped: 8 MFMAs per skipped k-step and four-tile wave iteration.
+//
+// Exactness.  Dropping a term fma(w, +0, acc) from a chain changes no bit of the chain's result
+// unless acc is a zero at that point, where the term can turn -0 into +0 (w finite: the pack
+// refuses non-finite weights).  A chain starts from +0 and reaches -0 only when a negative product
+// below 2^-150 in magnitude rounds to it.  From there on the two chains are either equal or both
+// zeros: a zero accumulator of either sign gives the same fma result for every nonzero product
+// (also one that rounds to a zero: its sign is the product's), and a zero for a zero product.  So
+// the chains end equal, or as zeros of different sign, and the bias add maps those to the same
+// bits: c + b = b for b != 0, and (+-0) + (+0) = +0; the pack refuses a bias of -0.  The
+// pre-activation, hence the clamped activation, is the full chain's bit for bit
+// (tests/test_prune_cpu.py checks the corner against the reference form of the chain).  The
+// same holds for the final layer's chain and bias.
+//
+// The check.  A skipped k-step's B operands are the activation registers that hold only
+// candidates (registers k >= ks of every lane group: position 4k + g); the clamp makes every
+// activation non-negative, so a register's bits are 0 exactly when its value is +0, and the
+// skipped registers of all layers are OR-ed into one flag (v_or3_b32).  A wave whose flag is
+// nonzero in any lane evaluates again in the original order, on the full pack from global memory
+// (mlp16_fp32_pruned below).  A -0 would only cause such a redo.
+//
+// ks (wave-uniform, from the kernarg segment: scalar registers) is at least 4, so k-steps 0-3 run
+// unconditionally; the others sit behind scalar branches in the unrolled loop, with static
+// register indices.  The final 32 -> 1 layer is the transposed form of mlp16_fp32_nt at every
+// tile count: positions 4k + g ascending = registers k outer, lane groups g inner.
+//
+// Registers (the batched fp32 tracer: 128 VGPRs, no scratch; tests/test_prune_cpu.py).  What it
+// took, each measured on the kernel's metadata: every branch an if without an else, the flag's ORs
+// in a region of their own after the k-steps (where k-steps and ORs met in an if-else hipcc wrote
+// the accumulator tuples to new registers and copied them back: 16 v_mov_b64 per layer, 23 spilled
+// VGPRs); the activations held as the 4-register vectors the MFMAs wrote (as 32 scalars they
+// fragmented the register file between the blocks: 13 spilled); k-steps 4-7 reading their own A
+// operands behind their branch.
+__device__ __forceinline__ int prune_ks(unsigned long long kb, int l) { return 4 + (int)((kb >> (3 * l)) & 7ull); }
+
+template <int NT>
+__device__ __forceinline__ float mlp16_fp32_pruned_nt(const float *__restrict__ s, int in0, int nh, unsigned long long kb,
+                                                      float fr, float x, float y, float z, uint32_t &flag) {
+    auto relu = [](float v) { return __builtin_amdgcn_fmed3f(v, 0.0f, 1.0f); };
+    const int lane = lane_id(), g = lane >> 4;
+    f32x4 av[NT][2];  // activations, register k = av[t][k >> 2][k & 3]
+    f32x4 c[NT][2];
+    uint32_t fl = 0;
+    auto skipped = [&](int k) {  // register k of every tile holds candidates only
+#pragma unroll
+        for (int t = 0; t < NT; t += 2) fl |= __float_as_uint(av[t][k >> 2][k & 3]) | __float_as_uint(av[t + 1 < NT ? t + 1 : t][k >> 2][k & 3]);
+    };
+    {
+        // layer 0 as in mlp16_fp32_nt
+        const float w0 = s[PK_L0W + lane], w1 = s[PK_L0W + 64 + lane];
+        uint32_t t0 = __float_as_uint(x), t1 = __float_as_uint(y), t2 = __float_as_uint(z);
+        uint32_t t3 = __float_as_uint(in0 == 4 ? fr : 0.0f);
+        auto r = __builtin_amdgcn_permlane32_swap(t0, t2, false, false);
+        t0 = r[0]; t2 = r[1];
+        r = __builtin_amdgcn_permlane32_swap(t1, t3, false, false);
+        t1 = r[0]; t3 = r[1];
+        r = __builtin_amdgcn_permlane16_swap(t0, t1, false, false);
+        t0 = r[0]; t1 = r[1];
+        r = __builtin_amdgcn_permlane16_swap(t2, t3, false, false);
+        t2 = r[0]; t3 = r[1];
+        const float bt[4] = {__uint_as_float(t0), __uint_as_float(t1), __uint_as_float(t2), __uint_as_float(t3)};
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            c[t][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0, bt[t], f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+            c[t][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1, bt[t], f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+        }
+        const float4 *bb = reinterpret_cast<const float4 *>(s + PK_L0B + g * 8);
+        const float4 blo = bb[0], bhi = bb[1];
+        const float bias[8] = {blo.x, blo.y, blo.z, blo.w, bhi.x, bhi.y, bhi.z, bhi.w};
+        const float s0 = s[pk_final(nh) + 33];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) av[t][mt][r] = relu(__builtin_fmaf(c[t][mt][r], s0, bias[4 * mt + r]));
+    }
+    for (int jl = 0; jl < nh; ++jl) {
+        const int ks = prune_ks(kb, jl);  // k-steps over the outputs of ReLU layer jl
+        const float *L = s + PK_HID + jl * PK_HID_STRIDE;
+        float4 wq[2];  // the A operands of k-steps 0-3
+#pragma unroll
+        for (int q = 0; q < 2; ++q) wq[q] = reinterpret_cast<const float4 *>(L)[q * 64 + lane];
+#pragma unroll
+        for (int st = 0; st < 8; ++st) {
+            if (st < 4 || st < ks) {
+                // (k-steps 4-7 read their two A operands here, behind their branch)
+                float2 w2 = {0.0f, 0.0f};
+                if (st >= 4) w2 = reinterpret_cast<const float2 *>(L)[((st >> 1) * 64 + lane) * 2 + (st & 1)];
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) {
+                    const int m = 2 * st + mt;
+                    const float4 wv = wq[st < 4 ? m >> 2 : 0];
+                    const float w4 = (m & 3) == 0 ? wv.x : ((m & 3) == 1 ? wv.y : ((m & 3) == 2 ? wv.z : wv.w));
+                    const float w = st < 4 ? w4 : (mt ? w2.y : w2.x);
+#pragma unroll
+                    for (int t = 0; t < NT; ++t)
+                        c[t][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                            w, av[t][st >> 2][st & 3], st == 0 ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : c[t][mt], 0, 0, 0);
+                }
+            }
+        }
+        if (ks < 8) {
+#pragma unroll
+            for (int k = 4; k < 8; ++k)
+                if (k >= ks) skipped(k);
+        }
+        const float4 *bb = reinterpret_cast<const float4 *>(L + 1024 + g * 8);
+        const float4 blo = bb[0], bhi = bb[1];
+        const float bias[8] = {blo.x, blo.y, blo.z, blo.w, bhi.x, bhi.y, bhi.z, bhi.w};
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) av[t][mt][r] = relu(c[t][mt][r] + bias[4 * mt + r]);
+    }
+    // final 32 -> 1: per register k, the 4x4 transpose of (tile, lane group) blocks puts positions
+    // 4k..4k+3 of point j of tile t in lane (j, t), then four links of the chain
+    const int ks = prune_ks(kb, nh);
+    const float4 *wf4 = reinterpret_cast<const float4 *>(s + pk_final(nh));
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        if (k < 4 || k < ks) {
+            uint32_t t0 = __float_as_uint(av[0][k >> 2][k & 3]), t1 = NT > 1 ? __float_as_uint(av[NT > 1 ? 1 : 0][k >> 2][k & 3]) : 0u;
+            uint32_t t2 = NT > 2 ? __float_as_uint(av[NT > 2 ? 2 : 0][k >> 2][k & 3]) : 0u;
+            uint32_t t3 = NT > 3 ? __float_as_uint(av[NT > 3 ? 3 : 0][k >> 2][k & 3]) : 0u;
+            auto r = __builtin_amdgcn_permlane32_swap(t0, t2, false, false);  // groups 2,3 <-> 0,1
+            t0 = r[0]; t2 = r[1];
+            r = __builtin_amdgcn_permlane32_swap(t1, t3, false, false);
+            t1 = r[0]; t3 = r[1];
+            r = __builtin_amdgcn_permlane16_swap(t0, t1, false, false);       // groups 1,3 <-> 0,2
+            t0 = r[0]; t1 = r[1];
+            r = __builtin_amdgcn_permlane16_swap(t2, t3, false, false);
+            t2 = r[0]; t3 = r[1];
+            const float4 w = wf4[k];
+            acc = __builtin_fmaf(w.x, __uint_as_float(t0), acc);
+            acc = __builtin_fmaf(w.y, __uint_as_float(t1), acc);
+            acc = __builtin_fmaf(w.z, __uint_as_float(t2), acc);
+            acc = __builtin_fmaf(w.w, __uint_as_float(t3), acc);
+        }
+    }
+    if (ks < 8) {
+#pragma unroll
+        for (int k = 4; k < 8; ++k)
+            if (k >= ks) skipped(k);
+    }
+    flag = fl;
+    return acc + s[pk_final(nh) + 32];
+}
+
+// The batched fp32 tracer's MLP.  s: the pack the workgroup staged in LDS -- the pruned pack when
+// M.pkp is set, else the full pack.  Waves of a scaled network whose inputs are within the bound
+// take the pruned form on their active tiles; a wave that then finds a candidate firing (redo = 1),
+// a wave with an input beyond the bound, and every wave of a network without a pruned pack take
+// the add + max form on all four tiles of the full pack -- read from global memory when LDS holds
+// the pruned one (four workgroups per CU leave no room for both).  On a scaled pack without -0
+// biases the add + max form gives the clamped form's bits for inputs within the bound (no
+// pre-activation is -0 or above 1), so the redo is the full pack's clamped evaluation bit for bit.
+__device__ __forceinline__ float mlp16_fp32_pruned(const MlpArgs &M, const float *s, float fr, float x, float y, float z,
+                                                   uint32_t tmask, uint32_t &redo) {
+    redo = 0;
+    if (M.pkp) {
+        if (M.f32_clamp && inputs_in_bound_f32(x, y, z, fr)) {
+            const int nt = 32 - __clz((int)tmask);  // highest active tile + 1
+            const unsigned long long kb = M.ks_bits;
+            uint32_t fl = 0;
+            float v;
+            if (nt >= 4) v = mlp16_fp32_pruned_nt<4>(s, M.in0, M.nh, kb, fr, x, y, z, fl);
+            else if (nt == 3) v = mlp16_fp32_pruned_nt<3>(s, M.in0, M.nh, kb, fr, x, y, z, fl);
+            else if (nt == 2) v = mlp16_fp32_pruned_nt<2>(s, M.in0, M.nh, kb, fr, x, y, z, fl);
+            else v = mlp16_fp32_pruned_nt<1>(s, M.in0, M.nh, kb, fr, x, y, z, fl);
+            if (__builtin_expect(__ballot(fl != 0) == 0, 1)) return v;
+            redo = 1;
+        }
+        // (a global-address-space pointer: global_load with a scalar base instead of flat_load with
+        // a 64-bit address per lane, which spilled the tracer's registers)
+        return mlp16_fp32_nt<4>((const float *)(const __attribute__((address_space(1))) float *)M.pk, M.in0, M.nh, fr, x, y, z);
+    }
+    return mlp16_fp32_nt<4>(s, M.in0, M.nh, fr, x, y, z);
 }
 
 // bf16 / fp16: the whole MLP on 32-point tiles, v_mfma_f32_32x32x16_{bf16,f16} (nr_internal.h
@@ -1083,8 +1274,10 @@ struct Smem16 {
 // workgroup's LDS (16.5 KB pack + stash + frames) lets 3 workgroups share a CU instead of 2
 // (bf16 C3 batch 2.09 -> 1.81 ms/frame, profiles/r2_lowp_clamp_lds_ab.txt).
 // smem16_bytes() is the matching dynamic-LDS size.
+// src32 (fp32 kernels): the fp32 pack to stage instead of M.pk, of the same size (the batched fp32
+// k_trace's pruned pack)
 template <int PREC, bool NEED32>
-__device__ __forceinline__ Smem16 stage16(const MlpArgs &M) {
+__device__ __forceinline__ Smem16 stage16(const MlpArgs &M, const float *src32 = nullptr) {
     constexpr bool lds32 = PREC == NR_PRECISION_FP32;
     Smem16 S;
     const int off = lds32 ? M.pk_bytes : 0;
@@ -1092,7 +1285,7 @@ __device__ __forceinline__ Smem16 stage16(const MlpArgs &M) {
     S.slp = reinterpret_cast<uint16_t *>(nr_smem16 + off);
     S.sfl = reinterpret_cast<float *>(nr_smem16 + off + M.lp_bytes);
     if constexpr (lds32) {
-        const int4 *src = reinterpret_cast<const int4 *>(M.pk);
+        const int4 *src = reinterpret_cast<const int4 *>(src32 ? src32 : M.pk);
         int4 *dst = reinterpret_cast<int4 *>(S.s32);
         for (int i = threadIdx.x; i < M.pk_bytes / 16; i += blockDim.x) dst[i] = src[i];
     }

@@ -286,6 +286,149 @@ bool pack_fp32_16(const std::vector<int> &dims, const std::vector<std::vector<fl
     return true;
 }
 
+// ---- the pruned fp32 pack (nr_internal.h PruneInfo; nr_mlp16.h mlp16_fp32_pruned) ----
+//
+// How often each unit of each ReLU layer fires (pre-activation > 0) over PRUNE_POINTS points drawn
+// uniformly from the ball the rays march in (radius 1.2, nr_device.h intersect_bounding), from a
+// fixed-seed splitmix64 sequence: a function of the network alone.  The evaluation is plain f32
+// (out-major accumulation, which vectorises): the counts steer speed only, never values.
+// 32,768 points resolve firing rates of ~3e-5.
+constexpr int PRUNE_POINTS = 32768;
+// Selection rule.  Units of a layer sorted by firing count, ascending, are
+// taken four at a time.  A group of four as candidates saves one k-step of the next layer: 8 MFMAs
+// of 32 cycles = 256 of the ~17,100 cycles of a four-tile wave iteration, 1.5 %.  It costs a redo --
+// the whole evaluation again in the add + max form on the full pack from global memory, ~1.5 wave
+// iterations -- whenever one of the four fires at one of the wave's 64 points: 64 x 1.5 x the
+// group's summed firing probability.  A group is taken while the saving exceeds the cost, i.e.
+// while its firings over the sample stay below 0.015 / 96 x PRUNE_POINTS (5), and the groups
+// before it were taken; at most PRUNE_MAX_CAND units per layer (k-steps 0-3 always run).
+constexpr double PRUNE_GROUP_RATE = 0.015 / (64.0 * 1.5);
+constexpr int PRUNE_MAX_CAND = 16;
+
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("O3")))  // vectorise the 32-wide inner loops
+#endif
+static void firing_counts(const std::vector<int> &dims, const std::vector<std::vector<float>> &K,
+                          const std::vector<std::vector<float>> &B, std::vector<std::vector<int>> &fired) {
+    const int nl = (int)dims.size() - 1;
+    uint64_t s = 0x6e727072756e6531ull;
+    auto unit = [&s]() {  // splitmix64 -> [0, 1)
+        uint64_t z = (s += 0x9e3779b97f4a7c15ull);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        return (double)((z ^ (z >> 31)) >> 11) * 0x1p-53;
+    };
+    fired.assign(nl - 1, std::vector<int>(32, 0));
+    float a[32], v[32];
+    for (int p = 0; p < PRUNE_POINTS; ++p) {
+        double x, y, z;
+        do {  // rejection: uniform in the ball
+            x = 2.0 * unit() - 1.0; y = 2.0 * unit() - 1.0; z = 2.0 * unit() - 1.0;
+        } while (x * x + y * y + z * z > 1.0);
+        a[0] = (float)(1.2 * x); a[1] = (float)(1.2 * y); a[2] = (float)(1.2 * z);
+        for (int l = 0; l < nl - 1; ++l) {
+            const int in = dims[l];
+            const float *Kl = K[l].data();
+            for (int u = 0; u < 32; ++u) v[u] = B[l][u];
+            for (int i = 0; i < in; ++i) {
+                const float ai = a[i];
+                if (ai == 0.0f) continue;
+                for (int u = 0; u < 32; ++u) v[u] += Kl[(size_t)i * 32 + u] * ai;
+            }
+            int *f = fired[l].data();
+            for (int u = 0; u < 32; ++u) {
+                f[u] += v[u] > 0.0f;
+                a[u] = v[u] > 0.0f ? v[u] : 0.0f;
+            }
+        }
+    }
+}
+
+bool pack_fp32_16_pruned(const std::vector<int> &dims, const std::vector<std::vector<float>> &Kin,
+                         const std::vector<std::vector<float>> &Bin, int mode, std::vector<float> &pack,
+                         PruneInfo &info) {
+    if (!fused_shape_ok(dims)) return false;
+    const int nl = (int)dims.size() - 1, nh = nl - 2, in0 = dims[0];
+    std::vector<int> e;
+    if (!clamp_scales(dims, Kin, Bin, e, (double)F32_INPUT_BOUND, 1, 0x1p-19)) return false;
+    // identity order, every k-step: the full pack's chains in this layout
+    info.nrelu = nh + 1;
+    info.cand.assign(nh + 1, 0);
+    info.ks.assign(nh + 1, 8);
+    info.order.resize((size_t)(nh + 1) * 32);
+    for (int l = 0; l <= nh; ++l)
+        for (int p = 0; p < 32; ++p) info.order[(size_t)l * 32 + p] = p;
+    // a pruned section needs: 3 inputs (the sample has no frame axis); finite weights (0 x inf is
+    // NaN, not the +0 the skip assumes); no bias of -0 (the exactness argument, nr_mlp16.h)
+    bool can = mode != 0 && in0 == 3;
+    for (int l = 0; l < nl && can; ++l) {
+        for (float w : Kin[l]) can = can && std::isfinite(w);
+        for (float b : Bin[l]) can = can && std::isfinite(b) && !(b == 0.0f && std::signbit(b));
+    }
+    if (can) {
+        std::vector<std::vector<int>> fired;
+        if (mode == 1) firing_counts(dims, Kin, Bin, fired);
+        for (int l = 0; l <= nh; ++l) {
+            std::vector<int> by(32);
+            for (int u = 0; u < 32; ++u) by[u] = u;
+            int c = 0;
+            if (mode == 1) {
+                std::stable_sort(by.begin(), by.end(), [&](int x, int y) { return fired[l][x] < fired[l][y]; });
+                while (c + 4 <= PRUNE_MAX_CAND) {
+                    long n = 0;
+                    for (int i = c; i < c + 4; ++i) n += fired[l][by[i]];
+                    if ((double)n >= PRUNE_GROUP_RATE * PRUNE_POINTS) break;
+                    c += 4;
+                }
+            } else {  // test mode: the four highest-numbered units, whatever their firing rate
+                std::reverse(by.begin(), by.end());
+                c = 4;
+            }
+            std::vector<char> is_cand(32, 0);
+            for (int i = 0; i < c; ++i) is_cand[by[i]] = 1;
+            int *ord = &info.order[(size_t)l * 32];
+            int n = 0;
+            for (int u = 0; u < 32; ++u) if (!is_cand[u]) ord[n++] = u;  // live, ascending
+            for (int u = 0; u < 32; ++u) if (is_cand[u]) ord[n++] = u;   // candidates
+            info.cand[l] = c;
+            info.ks[l] = (32 - c) / 4;
+        }
+    }
+    std::vector<std::vector<float>> K(Kin), B(Bin);
+    apply_scales(e, K, B);
+    K[0] = Kin[0];  // as pack_fp32_16: layer 0 unscaled, its chain scaled on the way out
+    pack.assign(pk_floats(nh), 0.0f);
+    pack[pk_final(nh) + 33] = std::ldexp(1.0f, -e[0]);
+    auto unit_at = [&](int l, int pos) { return info.order[(size_t)l * 32 + pos]; };
+    for (int mt = 0; mt < 2; ++mt)
+        for (int lane = 0; lane < 64; ++lane) {
+            const int i = lane & 15, kk = lane >> 4, gp = i >> 2, rp = i & 3;
+            const int uout = unit_at(0, 16 * mt + 4 * rp + gp);
+            pack[PK_L0W + mt * 64 + lane] = (kk < in0) ? K[0][(size_t)kk * 32 + uout] : 0.0f;
+        }
+    for (int g = 0; g < 4; ++g)
+        for (int k = 0; k < 8; ++k) pack[PK_L0B + g * 8 + k] = B[0][unit_at(0, 4 * k + g)];
+    for (int j = 0; j < nh; ++j) {
+        const std::vector<float> &Kj = K[j + 1];
+        const int base = PK_HID + j * PK_HID_STRIDE;
+        for (int st = 0; st < 8; ++st)
+            for (int mt = 0; mt < 2; ++mt) {
+                const int m = 2 * st + mt;
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int i = lane & 15, kk = lane >> 4, gp = i >> 2, rp = i & 3;
+                    const int uout = unit_at(j + 1, 16 * mt + 4 * rp + gp), uin = unit_at(j, 4 * st + kk);
+                    pack[base + ((m >> 2) * 64 + lane) * 4 + (m & 3)] = Kj[(size_t)uin * 32 + uout];
+                }
+            }
+        for (int g = 0; g < 4; ++g)
+            for (int k = 0; k < 8; ++k) pack[base + 1024 + g * 8 + k] = B[j + 1][unit_at(j + 1, 4 * k + g)];
+    }
+    const int fo = pk_final(nh);
+    for (int p = 0; p < 32; ++p) pack[fo + p] = K[nl - 1][unit_at(nh, p)];
+    pack[fo + 32] = B[nl - 1][0];
+    return true;
+}
+
 // The backward pack (nr_internal.h): the Keras kernels transposed into A operands.  Raw weights:
 // the gradient's chains are specified on them (include/neural_render.h, nr_mlp_gradient).
 bool pack_grad_16(const std::vector<int> &dims, const std::vector<std::vector<float>> &K, std::vector<float> &pack) {

@@ -285,7 +285,10 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
     const uint16_t *x3l = M.x3lp;
     const float *x3f = M.x3fl;
     if constexpr (X3L) stage_x3<PREC>(M, T.x3lp_bytes, T.x3fl_bytes, x3l, x3f);
-    Smem16 S = stage16<PREC, true>(M);  // (its __syncthreads also covers sf and the fp32x3 copy)
+    // PRN: the MLP on the pruned fp32 pack (nr_mlp16.h mlp16_fp32_pruned), staged in LDS instead of the
+    // full one, which the redo and the out-of-bound form read from global memory
+    constexpr bool PRN = RREG;
+    Smem16 S = stage16<PREC, true>(M, PRN ? M.pkp : nullptr);  // (its __syncthreads also covers sf and the fp32x3 copy)
     // converged rays per wave: {p.xyz, pixel} and the frame (the direction is regenerated from
     // the pixel for facingColor; matCapColor does not read it): 21 instead of 42 KB per CU,
     // so that 4 fp32 workgroups share a CU
@@ -347,6 +350,7 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
     // are at most its share of the launch's < 2^32 queue positions; its ray-steps can exceed that
     // (x max_steps), so they are flushed to the launch's counter past 2^30
     uint32_t nsteps = 0, nhit = 0, nconv = 0;
+    uint32_t nredo = 0;  // PRN: wave evaluations redone on the full pack (wave-uniform)
     uint32_t wit = 0, wit_tail = 0;  // wave iterations, those after the queue drained (stamps)
     // stamps: cycles in refill, shading, MLP, scene, step; and within refill: queue reservation,
     // bulk ray generation, dealing from the ring
@@ -371,6 +375,7 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
         rb_n = (uint32_t)__builtin_amdgcn_readfirstlane((int)rb_n);
         rb_head = (uint32_t)__builtin_amdgcn_readfirstlane((int)rb_head);
         if constexpr (EG) nfq = __builtin_amdgcn_readfirstlane(nfq);
+        if constexpr (PRN) nredo = (uint32_t)__builtin_amdgcn_readfirstlane((int)nredo);
         NR_PHASE(refill);
         // ---- refill free slots from the pixel queue
         if (!qempty || (RING && rb_n > 0)) {
@@ -733,10 +738,25 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
             // the shading loop into registers held for the kernel's life
             int zoff_x3 = 0;
             if constexpr (NX3) asm volatile("" : "+s"(zoff_x3));
-            const float sdf = NX3 ? mlp16_x3_normal<(EG ? NR_X3N_ONE_EG : NR_X3N_ONE) != 0>(M, S.s32, (X3L ? x3l : M.x3lp) + zoff_x3, (X3L ? x3f : M.x3fl) + zoff_x3, fr_of(sfr), pq.x, pq.y,
-                                                    pq.z, smask)
-                                  : mlp16_fp32(M, S.s32, fr_of(sfr), pq.x, pq.y, pq.z, smask);
-            const F3 cq = mul3s(tp, scene_sdf(pq, sdf, A.scene, zoff_of(sfr)));
+            float sdf;
+            if constexpr (PRN) {
+                uint32_t redo;
+                sdf = mlp16_fp32_pruned(fresh_kargs()->M, S.s32, fr_of(sfr), pq.x, pq.y, pq.z, smask, redo);
+                nredo += redo;
+            } else {
+                sdf = NX3 ? mlp16_x3_normal<(EG ? NR_X3N_ONE_EG : NR_X3N_ONE) != 0>(M, S.s32, (X3L ? x3l : M.x3lp) + zoff_x3, (X3L ? x3f : M.x3fl) + zoff_x3, fr_of(sfr), pq.x, pq.y,
+                                                        pq.z, smask)
+                          : mlp16_fp32(M, S.s32, fr_of(sfr), pq.x, pq.y, pq.z, smask);
+            }
+            // (PRN: the tetrahedron point formed again instead of held across the MLP, whose four-tile
+            // form leaves the shading pass no register for it)
+            F3 tq = tp;
+            if constexpr (PRN) {
+                int qr = q4;
+                asm volatile("" : "+v"(qr));
+                tq = mk3((qr == 0 || qr == 3) ? 1.0f : -1.0f, qr >= 2 ? 1.0f : -1.0f, (qr & 1) ? 1.0f : -1.0f);
+            }
+            const F3 cq = mul3s(tq, scene_sdf(pq, sdf, A.scene, zoff_of(sfr)));
             const F3 c1 = quad_bcast3_1(cq), c2 = quad_bcast3_2(cq), c3 = quad_bcast3_3(cq);
             if (k < nb && q4 == 0 && !T.itmap) {
                 const F3 nrm = normalize3(add3(add3(add3(cq, c1), c2), c3));
@@ -844,7 +864,16 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
             if (drained && nstash == 0 && nfq == 0) break;
             continue;
         }
-        uint32_t tmask = tiles_of(lm);
+        uint32_t tmask;
+        if constexpr (PRN) {
+            // (the upper half made opaque: hipcc otherwise joins the halves' tests into a 64-bit
+            // compare against 2^48, a constant it holds in a VGPR pair for the kernel's life)
+            uint32_t lo = (uint32_t)lm, hi = (uint32_t)(lm >> 32);
+            asm volatile("" : "+s"(hi));
+            tmask = ((lo & 0xffffu) ? 1u : 0u) | ((lo >> 16) ? 2u : 0u) | ((hi & 0xffffu) ? 4u : 0u) | ((hi >> 16) ? 8u : 0u);
+        } else {
+            tmask = tiles_of(lm);
+        }
         NR_PHASE(compaction);
         // ---- tail: pack the live rays into the lowest tiles
         if (drained) {
@@ -872,7 +901,14 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
         // ---- MLP on every live point, then one sphere-trace step per ray
         if (NONMLP_PRIO) __builtin_amdgcn_s_setprio(0);
         if (MLP_PRIO) set_priority(MLP_PRIO);
-        const float sdf = mlp16(M, S.s32, S.slp, S.sfl, prec, fr_of(rf), p.x, p.y, p.z, tmask, M.lp_clamp != 0);
+        float sdf;
+        if constexpr (PRN) {
+            uint32_t redo;
+            sdf = mlp16_fp32_pruned(fresh_kargs()->M, S.s32, fr_of(rf), p.x, p.y, p.z, tmask, redo);
+            nredo += redo;
+        } else {
+            sdf = mlp16(M, S.s32, S.slp, S.sfl, prec, fr_of(rf), p.x, p.y, p.z, tmask, M.lp_clamp != 0);
+        }
         NR_PHASE(step);
 #if NR_ARG_RELOAD
         const TraceKargs *K = fresh_kargs();
@@ -993,6 +1029,7 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
         if (maxit) atomicMax(T.stats + 2, (unsigned long long)maxit);
         if (EG && nfine) atomicAdd(T.stats + 4, (unsigned long long)nfine);
         if (EG && nswitch) atomicAdd(T.stats + 5, (unsigned long long)nswitch);
+        if (PRN && nredo) atomicAdd(T.stats + 6, (unsigned long long)nredo);
     }
 }
 

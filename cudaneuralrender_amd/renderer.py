@@ -19,6 +19,10 @@ def _fptr(a):
     return a.ctypes.data_as(_FP)
 
 
+def _iptr(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+
+
 CAMERA_MODES = {"f64": 0, "eigen": 1}
 
 
@@ -119,6 +123,31 @@ def pack_x3(dims, kernels, biases):
     check(L.nr_pack_x3(nl, d, kp, bp, a.ctypes.data, na.value, f.ctypes.data, nf.value, ctypes.byref(na),
                        ctypes.byref(nf), ctypes.byref(ok)))
     return a, f, ok.value
+
+
+def pack_fp32_pruned(dims, kernels, biases, mode=1):
+    """The library's fp32 packs of a fused-shape network (nr_pack_fp32_pruned; host only): a dict
+    with full (float32), clamp, and -- None / empty when the scaled pack is refused -- pruned
+    (float32), cand [nrelu], ks [nrelu] and order [nrelu][32] (position -> unit)."""
+    L = lib()
+    nl = len(kernels)
+    d = (ctypes.c_int * (nl + 1))(*dims)
+    ks_ = [np.ascontiguousarray(k, np.float32) for k in kernels]
+    bs = [np.ascontiguousarray(b, np.float32) for b in biases]
+    kp = (_FP * nl)(*[_fptr(k) for k in ks_])
+    bp = (_FP * nl)(*[_fptr(b) for b in bs])
+    n, cl, hp = ctypes.c_long(0), ctypes.c_int(0), ctypes.c_int(0)
+    args = (nl, d, kp, bp, int(mode))
+    check(L.nr_pack_fp32_pruned(*args, None, None, 0, ctypes.byref(n), ctypes.byref(cl), ctypes.byref(hp), None, None,
+                                None, 0))
+    nrelu = nl - 1
+    full, pruned = np.zeros(n.value, np.float32), np.zeros(n.value, np.float32)
+    cand, ks, order = np.zeros(nrelu, np.int32), np.zeros(nrelu, np.int32), np.zeros((nrelu, 32), np.int32)
+    check(L.nr_pack_fp32_pruned(*args, _fptr(full), _fptr(pruned), n.value, ctypes.byref(n), ctypes.byref(cl),
+                                ctypes.byref(hp), _iptr(cand), _iptr(ks), _iptr(order), nrelu))
+    if not hp.value:
+        return {"full": full, "clamp": cl.value, "pruned": None, "cand": cand[:0], "ks": ks[:0], "order": order[:0]}
+    return {"full": full, "clamp": cl.value, "pruned": pruned, "cand": cand, "ks": ks, "order": order}
 
 
 def shard_rows(H, band, nshards, shard):
@@ -297,6 +326,28 @@ class Renderer:
         march in fp32x3 (default NR_ENDGAME_DEFAULT = 1e-3; 0 = the pure 16-bit march)."""
         self._chk(self._L.nr_set_endgame(self._ctx, float(tau)))
         return self
+
+    def set_prune(self, mode):
+        """nr_set_prune: the batched fp32 tracer's skipping of never-firing hidden units: 0 off,
+        1 default, 2 test mode (four candidates per layer whatever they do).  Same frames and
+        statistics in every mode."""
+        self._chk(self._L.nr_set_prune(self._ctx, int(mode)))
+        return self
+
+    def prune_info(self):
+        """nr_prune_info: {cand [nrelu], ks [nrelu], order [nrelu][32]} of the loaded network's
+        pruned fp32 pack (empty arrays: none)."""
+        n = ctypes.c_int(0)
+        self._chk(self._L.nr_prune_info(self._ctx, ctypes.byref(n), None, None, None, 0))
+        cand, ks, order = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32), np.zeros((n.value, 32), np.int32)
+        self._chk(self._L.nr_prune_info(self._ctx, ctypes.byref(n), _iptr(cand), _iptr(ks), _iptr(order), n.value))
+        return {"cand": cand, "ks": ks, "order": order}
+
+    def prune_redos(self):
+        """nr_prune_redos: wave evaluations the last render_batch redid on the full fp32 pack."""
+        v = ctypes.c_ulonglong(0)
+        self._chk(self._L.nr_prune_redos(self._ctx, ctypes.byref(v)))
+        return int(v.value)
 
     def debug_stamps(self):
         """Per-wave stamps of the last k_trace: {start, queue drained, end (100 MHz ticks),

@@ -123,6 +123,17 @@ int nr_load_mlp(nr_ctx *ctx, int nlayers, const int *dims,
  * emulation (the bf16/fp16 tracers' normals); not part of the reference's interface. */
 int nr_pack_x3(int nlayers, const int *dims, const float *const *kernels, const float *const *biases,
                uint16_t *a, long a_cap, float *f, long f_cap, long *a_len, long *f_len, int *ok);
+/* The fp32 packs of a [3|4, 32, ..., 32, 1] network, host only (new symbols only: NR_ABI_VERSION
+ * stays 3): the full pack, and the pruned pack the batched fp32 tracer stages in LDS -- the same
+ * scaled weights with every ReLU layer's units re-ordered, live units ascending, then the cand[l]
+ * units that fire at next to no point of the marched volume (nr_set_prune for the modes).  *len =
+ * floats per pack (both), *clamp = the full pack is scaled for the clamped ReLU, *has_pruned = 0
+ * when that pack is refused (no pruned pack then).  cand, ks [nlayers - 1] and order
+ * [nlayers - 1][32] (position -> unit) are filled when cap_layers >= nlayers - 1; ks[l] = the
+ * k-steps of 4 positions that the layer after ReLU layer l runs while the candidates are +0. */
+int nr_pack_fp32_pruned(int nlayers, const int *dims, const float *const *kernels, const float *const *biases,
+                        int mode, float *full, float *pruned, long cap, long *len, int *clamp, int *has_pruned,
+                        int *cand, int *ks, int *order, int cap_layers);
 int nr_mlp_info(const nr_ctx *ctx, int *nlayers, int *dims /* >= nlayers+1 or NULL */,
                 int *num_weight_params, int *num_bias_params);
 int nr_set_precision(nr_ctx *ctx, int precision);
@@ -438,6 +449,19 @@ int nr_set_debug(nr_ctx *ctx, int flags);
  * IoU >= 0.99 / 0.98): 1e-3 (round 5's 3e-4 left C4's mean |delta| at 6.4). */
 #define NR_ENDGAME_DEFAULT 0.001f
 int nr_set_endgame(nr_ctx *ctx, float tau);
+/* The batched fp32 tracer (nr_render_batch at NR_PRECISION_FP32) skips the matrix-core k-steps of
+ * hidden units that never fire in the marched volume, checked per wave at run time: a wave that
+ * sees one fire evaluates again on the full pack, so frames and statistics are the same in every
+ * mode, bit for bit.  mode 0: no unit is a candidate (the A/B arm); 1 (default): candidates chosen
+ * when the network is loaded, from firing counts over a fixed sample (3-input networks with
+ * finite weights whose scaled pack is accepted; others have none); 2 (tests): the four
+ * highest-numbered units of every hidden layer, whatever they do, so that the redo runs
+ * constantly.  nr_prune_info: the loaded network's ReLU layers (*nrelu; 0: no pruned pack) and,
+ * when cap_layers >= *nrelu, the candidates per layer, the k-steps and the order [nrelu][32]
+ * (position -> unit).  nr_prune_redos: wave evaluations redone by the last nr_render_batch. */
+int nr_set_prune(nr_ctx *ctx, int mode);
+int nr_prune_info(const nr_ctx *ctx, int *nrelu, int *cand, int *ks, int *order, int cap_layers);
+int nr_prune_redos(nr_ctx *ctx, unsigned long long *redos);
 /* Temporal scheduling: each launch (a frame, or a batch's launch of up to 32 frames)
  * records its 8x8 pixel blocks' longest ray (the max over the batch's frames) and the next
  * launch of the same size/shard dispenses blocks longest-first (pixels are unaffected --
