@@ -21,6 +21,9 @@ NR_GROUP_COPY, NR_GROUP_ASYNC = 1, 2
 NR_ENDGAME_DEFAULT = 0.001  # include/neural_render.h: the bf16/fp16 endgame threshold by default
 # status of a queried ray (nr_trace_rays, nr_render_gbuffer)
 NR_RAY_MISS, NR_RAY_ESCAPED, NR_RAY_HIT, NR_RAY_LIMIT = 0, 1, 2, 3
+# nr_render_aa: which pixels are resolved from their S x S samples, and the default edge contrast
+NR_AA_MODE = {"adaptive": 0, "full": 1}
+NR_AA_CONTRAST_DEFAULT = 32
 
 # every symbol include/neural_render.h declares
 EXPORTS = [
@@ -35,7 +38,7 @@ EXPORTS = [
     "nr_h5_dims", "nr_h5_read_f32",
     "nr_group_create", "nr_group_destroy", "nr_group_size", "nr_group_render_batch", "nr_pack_x3",
     "nr_set_endgame", "nr_group_create_ex", "nr_group_synchronize", "nr_group_layout",
-    "nr_trace_rays", "nr_render_gbuffer",
+    "nr_trace_rays", "nr_render_gbuffer", "nr_render_aa",
     "nr_sample_grid", "nr_mesh_grid", "nr_extract_mesh", "nr_obj_save",
     "nr_mlp_gradient",
     "nr_pack_fp32_pruned", "nr_set_prune", "nr_prune_info", "nr_prune_redos",
@@ -124,6 +127,7 @@ def lib():
         "nr_render": (I, [P, P, I, I, I, I, ctypes.POINTER(NRStats)]),
         "nr_trace_rays": (I, [P, P, P, L64, I, P, P, P, P, P, I, ctypes.POINTER(NRStats)]),
         "nr_render_gbuffer": (I, [P, I, I, I, P, P, P, P, P, I, ctypes.POINTER(NRStats)]),
+        "nr_render_aa": (I, [P, P, I, I, I, I, I, I, I, ctypes.POINTER(L64), ctypes.POINTER(NRStats)]),
         "nr_sample_grid": (I, [P, FP, FP, IP, P, I, ctypes.POINTER(NRStats)]),
         "nr_mesh_grid": (I, [P, P, FP, FP, IP, F, P, L64, P, L64, ctypes.POINTER(L64), ctypes.POINTER(L64), I]),
         "nr_extract_mesh": (I, [P, FP, FP, IP, F, P, P, L64, P, L64, ctypes.POINTER(L64), ctypes.POINTER(L64), I,

@@ -90,6 +90,13 @@ struct nr_ctx {
     uint32_t *d_qs = nullptr;
     float *d_qio = nullptr;
     size_t cap_qio = 0;
+    // antialiasing (nr_render_aa): the sample cursor and the edge count on their own 128-byte lines
+    // + 4 x u64 stats; the edge list (4 B per pixel) and the accumulators (8 B per edge pixel)
+    uint32_t *d_aas = nullptr;
+    uint32_t *d_aalist = nullptr;
+    size_t cap_aalist = 0;
+    unsigned long long *d_aaacc = nullptr;
+    size_t cap_aaacc = 0;
     // volume sampling and isosurface extraction (nr_sample_grid, nr_mesh_grid, nr_extract_mesh):
     // the lattice of nr_extract_mesh (4 B per point; the staging of host lattices too), the
     // extraction's scratch (MeshArgs: 4 B per point + 24 B per 256 points) and the staging of
@@ -890,6 +897,7 @@ int nr_destroy(nr_ctx *c) {
     dfree(c->d_rargs); dfree(c->d_lsdf); dfree(c->d_lz);
     dfree(c->d_frames); dfree(c->d_bout);
     dfree(c->d_qs); dfree(c->d_qio);
+    dfree(c->d_aas); dfree(c->d_aalist); dfree(c->d_aaacc);
     dfree(c->d_grid); dfree(c->d_mesh); dfree(c->d_mio);
     if (c->h_frames) (void)hipHostFree(c->h_frames);
     if (c->ev_frames) (void)hipEventDestroy(c->ev_frames);
@@ -1435,6 +1443,129 @@ int nr_render_gbuffer(nr_ctx *c, int W, int H, int max_steps, int32_t *status, i
     if (max_steps < 1) return set_err(c, NR_E_INVALID, "nr_render_gbuffer: max_steps < 1");
     return query_rays(c, "nr_render_gbuffer", nullptr, nullptr, (long)W * H, W, H, max_steps, status, steps, t, position,
                       normal, loc, stats);
+}
+
+// ---- adaptive antialiasing (nr_aa.hip) ----
+
+// The base frame is nr_render's fp32 persistent render into the output buffer; the edge rule, the
+// sub-sample tracer and the resolve follow on the same stream.  One host read of the edge count
+// sizes the accumulators and the tracer's launch (none when there is no edge).
+constexpr int AA_BPC = 2;  // workgroups per CU of the sub-sample tracer's grid by default
+int nr_render_aa(nr_ctx *c, uint32_t *out, int W, int H, int samples, int mode, int contrast, int max_steps, int loc,
+                 long *edge_pixels, nr_stats *stats) {
+    if (!c || !out) return set_err(c, NR_E_INVALID, "nr_render_aa: NULL argument");
+    if (W < 1 || H < 1) return set_err(c, NR_E_INVALID, "nr_render_aa: bad size %dx%d", W, H);
+    if (samples < 1 || samples > 8) return set_err(c, NR_E_INVALID, "nr_render_aa: samples = %d outside 1..8", samples);
+    if (mode != NR_AA_ADAPTIVE && mode != NR_AA_FULL) return set_err(c, NR_E_INVALID, "nr_render_aa: unknown mode %d", mode);
+    if (contrast < 0 || contrast > 255) return set_err(c, NR_E_INVALID, "nr_render_aa: contrast = %d outside 0..255", contrast);
+    if ((long)samples * W > (1l << 30) || (long)samples * H > (1l << 30) ||
+        ((long)samples * W) * ((long)samples * H) > (1l << 30))
+        return set_err(c, NR_E_INVALID, "nr_render_aa: %d x %d samples of a %dx%d frame exceed 2^30", samples, samples, W, H);
+    if (max_steps < 0) return set_err(c, NR_E_INVALID, "nr_render_aa: max_steps < 0");
+    if (c->dims.empty()) return set_err(c, NR_E_STATE, "nr_render_aa: no network loaded");
+    if (!c->fused)
+        return set_err(c, NR_E_FORMAT, "nr_render_aa: needs a [3|4, 32, ..., 32, 1] network (no layered fallback)");
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const size_t npix = (size_t)W * H;
+    int rc;
+    uint32_t *dout = out;
+    if (loc != NR_DEVICE) {
+        if ((rc = ensure_buf(c, c->d_out, c->cap_out, npix)) != NR_OK) return rc;
+        dout = c->d_out;
+    }
+    // ---- the base frame: always the fp32 persistent tracer, the context's settings put back after it
+    nr_stats st{};
+    {
+        const int prec = c->precision, sched = c->schedule;
+        c->precision = NR_PRECISION_FP32;
+        c->schedule = NR_SCHED_PERSISTENT;
+        rc = nr_render_shard(c, dout, W, H, H, 1, 0, max_steps, NR_DEVICE, stats ? &st : nullptr);
+        c->precision = prec;
+        c->schedule = sched;
+        if (rc != NR_OK) return rc;
+    }
+    const int S = samples;
+    const bool full = mode == NR_AA_FULL;
+    long nedge = 0;
+    float ms_aa = 0.0f;
+    unsigned long long hs[4] = {0, 0, 0, 0};
+    if (S == 1) {
+        nedge = full ? (long)npix : 0;  // one sample per pixel: the base frame is the result
+    } else if (full || contrast < 255) {
+        if (!c->d_aas) HIPCHK(c, hipMalloc(&c->d_aas, 2 * 128 + 4 * 8));
+        if ((rc = ensure_buf(c, c->d_aalist, c->cap_aalist, npix)) != NR_OK) return rc;
+        AaArgs X{};
+        X.out = dout; X.W = W; X.H = H; X.S = S; X.per = S * S - 1;
+        X.contrast = contrast; X.full = full ? 1 : 0;
+        X.inv_w = 1.0 / (double)W; X.inv_s = 1.0 / (double)S; X.inv_per = 1.0 / (double)X.per;
+        X.list = c->d_aalist;
+        X.cursor = c->d_aas;
+        X.count = c->d_aas + 32;
+        X.stats = reinterpret_cast<unsigned long long *>(c->d_aas + 64);
+        if (stats) HIPCHK(c, hipEventRecord(c->ev0, s));
+        HIPCHK(c, hipMemsetAsync(c->d_aas, 0, 2 * 128 + 4 * 8, s));
+        HIPCHK(c, launch_aa_detect(X, s));
+        st.launches += 2;
+        uint32_t cnt = 0;
+        HIPCHK(c, hipMemcpyAsync(&cnt, X.count, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        nedge = (long)cnt;
+        if (cnt) {
+            if ((rc = ensure_buf(c, c->d_aaacc, c->cap_aaacc, (size_t)cnt)) != NR_OK) return rc;
+            X.accum = c->d_aaacc;
+            X.nedge = cnt;
+            X.inv_nedge = 1.0 / (double)cnt;
+            X.nsub = cnt * (uint32_t)X.per;  // < S W * S H <= 2^30
+            // the S W x S H frame's arguments, as nr_render builds them
+            RenderArgs A{};
+            A.out = nullptr; A.W = S * W; A.H = S * H; A.rows = A.H; A.band = A.H; A.nshards = 1; A.shard = 0;
+            A.max_steps = max_steps; A.scene = c->scene; A.frame = c->frame; A.color_type = c->color_type;
+            A.matcap = c->d_matcap; A.mw = c->mw; A.mh = c->mh;
+            set_recips(A);
+            memcpy(A.inv_view, c->inv_view, sizeof A.inv_view);
+            memcpy(A.normal, c->normal, sizeof A.normal);
+            // The grid by the CU count (nr_set_occupancy's workgroups per CU, or AA_BPC), at least 16
+            // samples per wave.  Edge samples are few and long: a launch whose samples fill at most 2x
+            // its waves' 64-ray slots is mostly tail, and there a wave fills only its 32 lowest lanes
+            // (or 16, when that deals every sample at once) and refills -- an iteration costs less the
+            // fewer tiles it holds (wave_rays_for's rule for the frame tracer; nr_set_wave_rays
+            // overrides, in whole tiles).  1024^2, S = 2, 92,820 samples: 1.94 ms at 64, 1.55 at 48,
+            // 1.34 at 32; S = 4, 464,100 samples: 4.03 at 64, 4.40 at 32.
+            const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : AA_BPC;
+            const size_t waves64 = ((size_t)X.nsub + 63) / 64;
+            const int grid = (int)std::max<size_t>(1, std::min<size_t>(waves64, (size_t)num_cus(c->device) * bpc));
+            const size_t slots = (size_t)grid * 4 * 64;
+            const size_t per_wave = ((size_t)X.nsub + (size_t)grid * 4 - 1) / ((size_t)grid * 4);
+            if (c->wave_rays > 0) X.take = std::min(64, (c->wave_rays + 15) / 16 * 16);
+            else X.take = (size_t)X.nsub > 2 * slots ? 64 : (per_wave <= 16 ? 16 : 32);
+            HIPCHK(c, hipMemsetAsync(c->d_aaacc, 0, (size_t)cnt * 8, s));
+            HIPCHK(c, launch_aa_trace(A, X, c->mlp16, grid, s));
+            HIPCHK(c, launch_aa_resolve(X, s));
+            st.launches += 3;
+            if (stats) HIPCHK(c, hipMemcpyAsync(hs, X.stats, sizeof hs, hipMemcpyDeviceToHost, s));
+        }
+        if (stats) {
+            HIPCHK(c, hipEventRecord(c->ev1, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+            HIPCHK(c, hipEventElapsedTime(&ms_aa, c->ev0, c->ev1));
+        }
+    }
+    if (loc != NR_DEVICE) {
+        HIPCHK(c, hipMemcpyAsync(out, dout, npix * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    if (edge_pixels) *edge_pixels = nedge;
+    if (stats) {
+        st.ray_steps += hs[0];
+        st.rays_hit += hs[1];
+        st.iterations = std::max(st.iterations, (int32_t)hs[2]);
+        st.rays_shaded += hs[3];
+        st.shade_evals += 4ull * hs[3];
+        st.ms_total += ms_aa;
+        *stats = st;
+    }
+    return NR_OK;
 }
 
 // ---- volume sampling and isosurface extraction (nr_mesh.hip) ----

@@ -169,6 +169,24 @@ struct QueryArgs {
     unsigned long long *stats;    // [0] ray-steps, [1] rays that entered the sphere, [2] max steps, [3] hits
 };
 
+// Adaptive antialiasing (nr_aa.hip; nr_render_aa): the W x H base frame in out, its edge pixels'
+// indices in list[0 .. *count) and one accumulator per list entry.
+struct AaArgs {
+    uint32_t *out;                // [H][W]: the base frame, resolved in place
+    int W, H, S;                  // S x S samples per edge pixel, S W * S H <= 2^30
+    int per;                      // S S - 1: the samples the tracer adds to sample (0, 0)
+    int contrast, full;           // the edge rule's threshold; full: every pixel is an edge
+    double inv_w, inv_s, inv_per; // 1/W, 1/S, 1/per for udiv_r
+    double inv_nedge;             // 1/nedge
+    uint32_t *list;               // [W H]: edge pixels y W + x, in the order the appends landed
+    uint32_t *count;              // their number (zeroed before k_aa_detect)
+    uint32_t nedge, nsub;         // *count and *count x per once the host has read it
+    unsigned long long *accum;    // [nedge]: r, g, b, a sums in four 16-bit fields (zeroed before k_aa_trace)
+    uint32_t *cursor;             // next sample to deal (zeroed before the launch)
+    int take;                     // lanes a wave of k_aa_trace fills, 16..64
+    unsigned long long *stats;    // [0] ray-steps, [1] rays that entered the sphere, [2] max iterations, [3] coloured
+};
+
 // The lattice of nr_sample_grid / nr_mesh_grid / nr_extract_mesh: point (i, j, k) has linear index
 // (k ny + j) nx + i and coordinates origin[a] + (float)idx_a * step[a] (one f32 multiply, one add).
 struct LatticeArgs {
@@ -235,6 +253,9 @@ hipError_t launch_vnormal(const VNormalArgs &V, const MlpArgs &M, int grid, hipS
 hipError_t launch_mesh_count(const MeshArgs &A, hipStream_t st);  // k_mesh_count, then k_mesh_scan
 hipError_t launch_mesh_emit(const MeshArgs &A, hipStream_t st);
 hipError_t launch_query(const QueryArgs &Q, const MlpArgs &M, int grid, hipStream_t st);
+hipError_t launch_aa_detect(const AaArgs &X, hipStream_t st);
+hipError_t launch_aa_trace(const RenderArgs &A, const AaArgs &X, const MlpArgs &M, int grid, hipStream_t st);  // 4-wave workgroups
+hipError_t launch_aa_resolve(const AaArgs &X, hipStream_t st);
 hipError_t launch_dense(const DenseArgs &D, int src, int grid, hipStream_t st);
 hipError_t launch_init_f(const RenderArgs &A, const FrameArgs *F, const QueueArgs &Q, long npix, long total,
                          int grid, hipStream_t st);

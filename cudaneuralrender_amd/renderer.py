@@ -9,8 +9,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (NR_COLOR_FACING, NR_COLOR_MATCAP, NR_DEVICE, NR_GROUP_ASYNC, NR_GROUP_COPY, NR_HOST, NR_PRECISION,
-                   NR_SCENE, NR_SCHEDULE, NRFrame, NRKernelProf, NRStats, check, lib)
+from ._lib import (NR_AA_CONTRAST_DEFAULT, NR_AA_MODE, NR_COLOR_FACING, NR_COLOR_MATCAP, NR_DEVICE, NR_GROUP_ASYNC,
+                   NR_GROUP_COPY, NR_HOST, NR_PRECISION, NR_SCENE, NR_SCHEDULE, NRFrame, NRKernelProf, NRStats, check, lib)
 
 _FP = ctypes.POINTER(ctypes.c_float)
 
@@ -480,6 +480,35 @@ class Renderer:
         if not normals:
             del out["normal"]
         return (out, st.as_dict()) if with_stats else out
+
+    # -- adaptive supersampled antialiasing
+    def _render_aa(self, out, W, H, samples, mode, contrast, max_steps, loc, with_stats):
+        st = NRStats()
+        edges = ctypes.c_long(0)
+        self._chk(self._L.nr_render_aa(self._ctx, out, int(W), int(H), int(samples), NR_AA_MODE[mode], int(contrast),
+                                       int(max_steps), loc, ctypes.byref(edges),
+                                       ctypes.byref(st) if with_stats else None))
+        d = st.as_dict() if with_stats else {}
+        d["edge_pixels"] = edges.value
+        return d
+
+    def render_aa(self, W, H, samples=2, mode="adaptive", contrast=NR_AA_CONTRAST_DEFAULT, max_steps=6000,
+                  with_stats=True):
+        """nr_render_aa: the W x H frame with its edge pixels (mode "adaptive": those whose
+        8-neighbourhood differs by more than ``contrast`` in some channel; "full": every pixel) box-
+        filtered from samples x samples sub-pixel rays -- the pixels of render()'s samples W x samples H
+        frame.  Alpha becomes coverage, colours come out premultiplied.  Always the fp32 MLP.  Returns
+        (image, stats) with stats["edge_pixels"]."""
+        out = np.zeros((H, W), np.uint32)
+        st = self._render_aa(out.ctypes.data, W, H, samples, mode, contrast, max_steps, NR_HOST, with_stats)
+        return (out, st) if with_stats else out
+
+    def render_aa_device(self, out_ptr, W, H, samples=2, mode="adaptive", contrast=NR_AA_CONTRAST_DEFAULT,
+                         max_steps=6000, with_stats=False):
+        """nr_render_aa into a device buffer of W * H uint32 (e.g. a torch tensor's data_ptr()), on the
+        context's stream (set_stream).  Returns the stats dict when asked for, else the edge-pixel count."""
+        st = self._render_aa(ctypes.c_void_p(out_ptr), W, H, samples, mode, contrast, max_steps, NR_DEVICE, with_stats)
+        return st if with_stats else st["edge_pixels"]
 
     # -- volume sampling / isosurface extraction
     def sample_grid(self, origin, step, dims, with_stats=False):

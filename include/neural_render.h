@@ -206,6 +206,53 @@ int nr_trace_rays(nr_ctx *ctx, const float *origins /*[n][3]*/, const float *dir
 int nr_render_gbuffer(nr_ctx *ctx, int W, int H, int max_steps, int32_t *status, int32_t *steps, float *t,
                       float *position, float *normal, int loc, nr_stats *stats);
 
+/* ---- adaptive supersampled antialiasing ---------------------------------------- */
+/* (a new symbol only, as the ray queries: NR_ABI_VERSION stays 3) */
+#define NR_AA_ADAPTIVE 0
+#define NR_AA_FULL 1
+#define NR_AA_CONTRAST_DEFAULT 32
+/* Renders the W x H frame of the context's view with the edge pixels resolved from S x S samples,
+ * S = samples, 1 <= S <= 8.  Let `big` be the frame nr_render gives for S W x S H with the context's
+ * view, frame number, scene, colouring and matcap at NR_PRECISION_FP32 and max_steps, and
+ * base[y][x] = big[S y][S x] -- which is nr_render's W x H frame: sub-sample (0, 0) of pixel (x, y)
+ * has that pixel's ray.  The antialiased frame is a box filter over `big`, applied where the base
+ * frame shows an edge:
+ *  1. Channels.  A pixel is (r, g, b, a) = bits 0-7, 8-15, 16-23, 24-31; a background, missed or
+ *     unconverged pixel is 0 in all four.
+ *  2. Edge.  Pixel (x, y) is an edge iff some pixel n of its 8-neighbourhood that lies inside the
+ *     image has max over the four channels of |base(x, y) - base(n)| > contrast (strict; 0 <=
+ *     contrast <= 255).  Neighbours outside the image do not exist: a frame border is not an edge.
+ *     A coloured pixel has alpha 255 next to the background's 0, so every contrast below 255 finds
+ *     the silhouette and lower values add creases and shading gradients; contrast = 255 finds no
+ *     edge.  NR_AA_FULL treats every pixel as an edge.
+ *  3. Resolve.  Each channel of an edge pixel is (sum + S S / 2) / (S S) in integer arithmetic, the
+ *     sum over that channel of the S S pixels big[S y + sy][S x + sx]: alpha becomes coverage and
+ *     the colours come out premultiplied against a transparent black background.  Any other pixel
+ *     is base(x, y) unchanged.
+ *  4. Arithmetic and settings.  Always the fp32 MLP: nr_set_precision and nr_set_schedule are
+ *     ignored, as for the ray queries, and the call leaves the context's settings as it found
+ *     them.  The output depends only on the inputs: the same bits on every call, for any grid size
+ *     or order in which the samples are dealt (the sums are integer).
+ *  5. Outputs.  *edge_pixels (may be NULL) = the number of edge pixels (W H in FULL mode; 0 in
+ *     adaptive mode with S = 1, where no pixel is resolved).  stats (may be NULL): ray_steps,
+ *     shade_evals, rays_hit and rays_shaded are the base frame's plus those of the additional
+ *     sub-sample rays -- in FULL mode nr_render's for the S W x S H frame; iterations is the larger
+ *     of the two passes'; launches and ms_total as elsewhere.
+ *  6. Errors.  NR_E_INVALID: ctx or out NULL, W or H < 1, S outside 1..8, an unknown mode, contrast
+ *     outside 0..255, S W * S H > 2^30, max_steps < 0.  NR_E_STATE: no network.  NR_E_FORMAT: a
+ *     network the fused kernels do not take, as for the queries (no layered fallback).  Everything
+ *     else nr_render would report for the same context is reported as nr_render reports it.
+ *  7. Limitation.  Adaptive mode only refines what the base samples reveal: a feature thinner than
+ *     a pixel that no base ray hits is not found.  NR_AA_FULL is the exact form.
+ *  8. Scratch.  The context owns it and keeps it until nr_destroy: 4 bytes per pixel (the edge
+ *     list) and 8 bytes per edge pixel (the accumulators), plus W H x 4 bytes of staging for a host
+ *     output.  The S W x S H image is never materialised.
+ * With S = 1, contrast = 255 (adaptive) or no edge pixel the result is the base frame and no
+ * sub-sample pass is launched.  The call reads the edge count on the host once (it synchronises the
+ * context's stream) before it launches the sub-sample pass. */
+int nr_render_aa(nr_ctx *ctx, uint32_t *out, int W, int H, int samples, int mode, int contrast,
+                 int max_steps, int out_loc, long *edge_pixels, nr_stats *stats);
+
 /* ---- volume sampling / isosurface extraction ------------------------------------ */
 /* (new symbols only, as the ray queries: NR_ABI_VERSION stays 3)
  *

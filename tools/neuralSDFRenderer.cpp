@@ -6,7 +6,8 @@
 // viewer (:480-519) needs a display and is not built; extra flags: --max-steps,
 // --precision {fp32,bf16,fp16,fp32x3}, --scene {v1,tanh}, --ppm (also write a .ppm),
 // --camera {eigen,f64}, --gpus N (each frame's row-band shards on N GPUs, one RCCL gather:
-// nr_group_render_batch).
+// nr_group_render_batch), --aa S / --aa-full / --aa-contrast N (the single-GPU frame antialiased
+// from S x S samples per edge pixel, or per pixel: nr_render_aa).
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -41,6 +42,9 @@ static int cameraMode = NR_CAMERA_F64;
 // --gpus N: every frame split into row-band shards over GPUs 0..N-1 of this process (one context
 // per GPU, nr_group: one RCCL gather per frame); 0 = the reference's single-GPU render_kernel path
 static int numGpus = 0;
+// --aa S: the frame through nr_render_aa with S x S samples (0 = nr_render, as without the flag);
+// --aa-full: every pixel instead of the edge pixels; --aa-contrast N: the edge rule's threshold
+static int aaSamples = 0, aaMode = NR_AA_ADAPTIVE, aaContrast = NR_AA_CONTRAST_DEFAULT;
 static std::vector<nr_ctx *> groupCtx;
 static nr_group *group = nullptr;
 
@@ -67,7 +71,9 @@ static void usage() {
                  "\t--animation 4-input networks (frame number as 4th input)\n"
                  "\t--max-steps N (default 6000)  --precision fp32|bf16|fp16|fp32x3  --scene v1|tanh  --ppm\n"
                  "\t--camera f64|eigen (default f64: exact matrices rounded once; eigen: a restatement of Eigen's scalar float path, unpinned)\n"
-                 "\t--gpus N split every frame into row-band shards over N GPUs (one RCCL gather per frame)\n";
+                 "\t--gpus N split every frame into row-band shards over N GPUs (one RCCL gather per frame)\n"
+                 "\t--aa S antialias edge pixels from S x S samples (1..8; single GPU, always fp32)  --aa-full every pixel\n"
+                 "\t--aa-contrast N edge threshold 0..255 (default 32)\n";
 }
 
 static void parseCmdOptions(int argc, char **argv) {
@@ -88,6 +94,9 @@ static void parseCmdOptions(int argc, char **argv) {
     if (getCmdOption(b, e, "--camera")) cameraMode = std::string(getCmdOption(b, e, "--camera")) == "eigen" ? NR_CAMERA_EIGEN : NR_CAMERA_F64;
     if (cmdOptionExists(b, e, "--animation")) numInputs = 4;
     if (getCmdOption(b, e, "--gpus")) numGpus = std::max(0, atoi(getCmdOption(b, e, "--gpus")));
+    if (getCmdOption(b, e, "--aa")) aaSamples = atoi(getCmdOption(b, e, "--aa"));
+    if (cmdOptionExists(b, e, "--aa-full")) aaMode = NR_AA_FULL;
+    if (getCmdOption(b, e, "--aa-contrast")) aaContrast = atoi(getCmdOption(b, e, "--aa-contrast"));
     if (getCmdOption(b, e, "--max-steps")) NR_MAX_STEPS = atoi(getCmdOption(b, e, "--max-steps"));
     if (getCmdOption(b, e, "--scene")) NR_SCENE_MODE = std::string(getCmdOption(b, e, "--scene")) == "tanh" ? NR_SCENE_TANH : NR_SCENE_V1;
     if (getCmdOption(b, e, "--precision")) {
@@ -127,6 +136,24 @@ static bool groupInit() {
     return true;
 }
 
+// The frame through nr_render_aa on the network's context, with the settings render_kernel applies.
+static bool renderAA(unsigned *d_output, const float *invView, const float *normal) {
+    nr_ctx *c = nn.context();
+    long edges = 0;
+    if (!c || nr_set_view(c, invView, normal, frameNumber) != NR_OK || nr_set_static(c, colorType, numInputs) != NR_OK ||
+        nr_set_scene(c, NR_SCENE_MODE) != NR_OK ||
+        (colorType == NR_COLOR_MATCAP &&
+         nr_set_matcap(c, matcap.hostData.get(), (int)matcap.shape.x, (int)matcap.shape.y) != NR_OK) ||
+        nr_render_aa(c, d_output, (int)width, (int)height, aaSamples, aaMode, aaContrast, NR_MAX_STEPS, NR_DEVICE, &edges,
+                     nullptr) != NR_OK ||
+        nr_synchronize(c) != NR_OK) {
+        printf("nr_render_aa: %s\n", nr_last_error(c));
+        return false;
+    }
+    if (saveCount == 0) printf("antialiasing: %d x %d samples on %ld edge pixels\n", aaSamples, aaSamples, edges);
+    return true;
+}
+
 static bool generateSingleImage() {
     if (numGpus > 0) {  // the frame across numGpus GPUs
         if (!group && !groupInit()) return false;
@@ -157,7 +184,11 @@ static bool generateSingleImage() {
     (void)hipDeviceSynchronize();
     auto t0 = std::chrono::steady_clock::now();
     dim3_ block{8, 8, 1}, grid{(width + 7) / 8, (height + 7) / 8, 1};
-    render_kernel(grid, block, d_output, width, height, (unsigned)numInputs, nn, matcap);
+    if (aaSamples > 0) {
+        if (!renderAA(d_output, invView, normal)) return false;
+    } else {
+        render_kernel(grid, block, d_output, width, height, (unsigned)numInputs, nn, matcap);
+    }
     (void)hipDeviceSynchronize();
     double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (saveCount == 0)
