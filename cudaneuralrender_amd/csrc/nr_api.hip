@@ -169,10 +169,10 @@ int set_err(nr_ctx *c, int code, const char *fmt, ...) {
 // 0.519 ms/frame, one 8-way shard: 0.087 -> 0.081), fp32 once a launch holds >= 8 M pixels
 // (1024^2 x 32: 1.961 -> 1.908; one 8-way shard x 32 frames, 4 M: 0.290 vs 0.293).
 // Measurements: profiles/r1_ab_experiments.txt.
-int spread_for(const nr_ctx *c, int nframes, size_t npix) {
+int spread_for(const nr_ctx *c, int prec, int nframes, size_t npix) {
     if (c->spread >= 0) return c->spread;
     if (nframes < 4) return 16;
-    if (c->precision != NR_PRECISION_FP32) return 0;
+    if (prec != NR_PRECISION_FP32) return 0;
     return (size_t)nframes * npix >= ((size_t)8 << 20) ? 0 : 16;
 }
 
@@ -186,6 +186,37 @@ int nr::report_error(int code, const char *fmt, ...) {
     va_end(ap);
     g_err = buf;
     return code;
+}
+
+// ---- shard and batch geometry (exported: the callers that split frames use the same rules) ----
+
+int nr_shard_rows(int H, int band, int nshards, int shard) {
+    if (H < 0 || band < 1 || nshards < 1 || shard < 0 || shard >= nshards) return 0;
+    int full = H / band, rem = H % band;
+    int rows = (full / nshards) * band;
+    int extra = full % nshards;               // bands beyond the complete rounds
+    if (shard < extra) rows += band;
+    if (shard == extra && rem) rows += rem;   // the partial last band
+    return rows;
+}
+
+// Queue positions are uint32 (pix_ctr atomics in k_trace): one launch hands out
+// shard_total = blocks of the busiest queue shard x 64 x frames positions.  Past a shard's end
+// a wave of the low-precision tracers can take two pending reservations of up to 64 positions
+// (NR_QUEUE_CHUNK_DENSE: one absorbed and found past the end while the wave still had positions
+// of its pool, the next requested right after) and one blocking reservation of up to 64 before
+// it moves on: with the grid nr_set_occupancy allows (16 workgroups x 4 waves per CU) on up to
+// 512 CUs the over-reservation stays below 512 x 16 x 4 x 192 = 6,291,456 (ADVICE r2: the old
+// 2^19 assumed 8 workgroups and no pending reservation).
+int nr_batch_frames_per_launch(int W, int H, int band, int nshards, int shard, int nframes, int queue_shards) {
+    if (W < 1 || H < 1 || nframes < 1 || queue_shards < 1) return 0;
+    const int rows = nr_shard_rows(H, band, nshards, shard);
+    if (rows < 1) return std::min(nframes, NR_MAX_BATCH);
+    const long long nblocks = (long long)((W + 7) / 8) * ((rows + 7) / 8);
+    const long long per_frame = ((nblocks + queue_shards - 1) / queue_shards) * 64;  // busiest shard
+    const long long slop = 512ll * 16 * 4 * (64 + 2 * 64);
+    const long long cap = ((1ll << 32) - 1 - slop) / per_frame;
+    return (int)std::min<long long>(std::min(nframes, NR_MAX_BATCH), cap);
 }
 
 namespace {
@@ -432,14 +463,75 @@ int num_cus(int dev) {
     return cus;
 }
 
+// The context's stream: the caller's (nr_set_stream) or the private one, created here on
+// first use.  Returns NULL only if that creation failed (error recorded).
+#define GET_STREAM(c, s)                                           \
+    hipStream_t s = cur_stream(c);                                 \
+    if ((c)->use_own && !(c)->own_stream) return NR_E_HIP;
+
+hipStream_t cur_stream(nr_ctx *c) {
+    if (c->use_own && !c->own_stream) {
+        if (hipSetDevice(c->device) != hipSuccess ||
+            hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
+            c->own_stream = nullptr;
+            set_err(c, NR_E_HIP, "stream creation failed");
+            return nullptr;
+        }
+        c->stream = c->own_stream;
+    }
+    return c->stream;
+}
+
+// The end of a timed call whose launches lie between ev0 and ev1: with statistics wanted,
+// synchronise and read the time; without, synchronise only if results went to the host.
+int end_timed(nr_ctx *c, bool timed, int loc, hipStream_t s, float *ms) {
+    if (timed) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        HIPCHK(c, hipEventElapsedTime(ms, c->ev0, c->ev1));
+    } else if (loc != NR_DEVICE) {
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    return NR_OK;
+}
+
+// ---- what every frame render checks and fills (nr_render_shard, nr_render_batch, nr_render_aa) ----
+
+int check_shape(nr_ctx *c, int W, int H, int band, int nshards, int shard, int max_steps) {
+    if (W < 1 || H < 1 || (long)W * H > (1l << 31)) return set_err(c, NR_E_INVALID, "nr_render: bad size %dx%d", W, H);
+    if (band < 1 || nshards < 1 || shard < 0 || shard >= nshards) return set_err(c, NR_E_INVALID, "nr_render: bad shard");
+    if (max_steps < 0) return set_err(c, NR_E_INVALID, "nr_render: max_steps < 0");
+    return NR_OK;
+}
+
+// network, inputs and matcap
+int check_scene(nr_ctx *c) {
+    if (c->dims.empty()) return set_err(c, NR_E_STATE, "nr_render: no network loaded");
+    if (c->dims.back() != 1)
+        return set_err(c, NR_E_FORMAT, "nr_render: the SDF network must have one output (has %d)", c->dims.back());
+    if (c->dims[0] != c->num_inputs)
+        return set_err(c, NR_E_STATE, "nr_render: network takes %d inputs but numInputs = %d", c->dims[0], c->num_inputs);
+    if (c->color_type == NR_COLOR_MATCAP && !c->d_matcap) return set_err(c, NR_E_STATE, "nr_render: matcap colouring without a matcap");
+    return NR_OK;
+}
+
+// The RenderArgs every schedule shares: the shard image, scene, colouring and matcap.  The caller
+// adds out, frame and the view where one launch has them (a batch's are in its FrameArgs).
+RenderArgs render_args(const nr_ctx *c, int W, int H, int rows, int band, int nshards, int shard, int max_steps) {
+    RenderArgs A{};
+    A.W = W; A.H = H; A.rows = rows; A.band = band; A.nshards = nshards; A.shard = shard;
+    A.max_steps = max_steps; A.scene = c->scene; A.color_type = c->color_type;
+    A.matcap = c->d_matcap; A.mw = c->mw; A.mh = c->mh;
+    set_recips(A);
+    return A;
+}
 
 int read_queue_counters(nr_ctx *c, int max_steps, nr_stats &st, hipStream_t s);
 
 // The endgame's threshold for a persistent render (TraceArgs::eg_tau): nr_set_endgame's, for the
 // bf16/fp16 tracers with fp32x3 normals (the fine passes use their fp32x3 pack) and iteration
 // counts that fit the fine queue's 24 bits; 0 otherwise (the pure 16-bit march)
-static float endgame_tau(const nr_ctx *c, int max_steps) {
-    const bool lowp = c->precision == NR_PRECISION_BF16 || c->precision == NR_PRECISION_FP16;
+static float endgame_tau(const nr_ctx *c, int prec, int max_steps) {
+    const bool lowp = prec == NR_PRECISION_BF16 || prec == NR_PRECISION_FP16;
     return lowp && c->mlp16.x3n && max_steps < (1 << 24) ? c->eg_tau : 0.0f;
 }
 
@@ -450,11 +542,11 @@ static float endgame_tau(const nr_ctx *c, int max_steps) {
 //   bf16/fp16 (<= 128 VGPRs, 31 KB): 2 under 1 M pixels, 3 under 2 M (a 1024^2 frame: 0.885 /
 //         0.843 / 0.856 ms at 2 / 3 / 4), else 4 (1024^2 x 20: 0.424 -> 0.404 ms/frame at 3 -> 4,
 //         2048^2 x 8: 1.661 -> 1.569, one 2048^2 frame 2.503 -> 2.481).
-int default_bpc(const nr_ctx *c, size_t total, int nframes) {
+int default_bpc(int prec, size_t total, int nframes) {
     const size_t M = (size_t)1 << 20;
     // fp32x3: its k_trace instance is built for 3 waves per SIMD (168 VGPRs)
-    if (c->precision == NR_PRECISION_FP32X3) return total < M ? 2 : 3;
-    if (c->precision == NR_PRECISION_FP32) {
+    if (prec == NR_PRECISION_FP32X3) return total < M ? 2 : 3;
+    if (prec == NR_PRECISION_FP32) {
         if (nframes < 4 || total < M) return 2;
         return total >= 8 * M ? 4 : 3;
     }
@@ -467,8 +559,8 @@ int default_bpc(const nr_ctx *c, size_t total, int nframes) {
 // instances march without the endgame, launch_trace_k) NR_TRACE_BPC_EG 4-wave workgroups' worth:
 // with NR_EG_WAVES > 4 exactly that -- launch_trace_k runs them as one NR_EG_WAVES-wave workgroup
 // per CU, and fewer would leave CUs idle -- else at most that
-int trace_bpc(const nr_ctx *c, size_t total, int nframes, bool eg) {
-    const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : default_bpc(c, total, nframes);
+int trace_bpc(const nr_ctx *c, int prec, size_t total, int nframes, bool eg) {
+    const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : default_bpc(prec, total, nframes);
     if (eg) return NR_EG_WAVES > 4 ? NR_TRACE_BPC_EG : std::min(bpc, NR_TRACE_BPC_EG);
     return bpc;
 }
@@ -479,9 +571,9 @@ int trace_bpc(const nr_ctx *c, size_t total, int nframes, bool eg) {
 // 8 row-band shards: 1.015 -> 0.854 ms, on 4 shards 1.139 -> 1.124; on 2 shards or whole frames
 // 32 is slower, and bf16, whose tiles are cheap, gains nothing; profiles/r3_ab_experiments.txt
 // (24), (25)).
-int wave_rays_for(const nr_ctx *c, size_t pixels, int grid) {
+int wave_rays_for(const nr_ctx *c, int prec, size_t pixels, int grid) {
     if (c->wave_rays > 0) return c->wave_rays;
-    if (c->precision == NR_PRECISION_FP32 && pixels <= 2 * (size_t)grid * 4 * 64) return 32;
+    if (prec == NR_PRECISION_FP32 && pixels <= 2 * (size_t)grid * 4 * 64) return 32;
     return 64;
 }
 
@@ -501,9 +593,89 @@ int order_buffers(nr_ctx *c, int W, int H, int band, int nshards, int shard, int
     return NR_OK;
 }
 
-// Per-frame arguments of a batch: pinned staging (reused only once the previous upload
-// has been consumed) + device copy.  With host outputs the frames of one launch go
-// through d_bout (`chunk` frames).
+// ---- the persistent tracer's launch (k_trace), shared by its single-frame and batched drivers ----
+
+// d_tr: one set of NR_MAX_QUEUES shard counters on their own 128-byte lines, then 8 x u64 stats
+// (allocated twice over: the cost probe's launch has a set of its own)
+constexpr size_t TR_BYTES = NR_MAX_QUEUES * 128 + 8 * 8;
+
+inline uint64_t lane_cap_for(int take) { return take >= 64 ? ~0ull : (1ull << take) - 1ull; }
+
+// The TraceArgs that follow from the shard image (W x rows, bands of `band` rows) and the context,
+// whatever the launch: counters and statistics in d_tr, the queue geometry -- the pixel spread is
+// chosen for the whole call's `nframes` frames of `npix` pixels -- the endgame's threshold and
+// the fp32x3 pack sizes.
+int trace_args(nr_ctx *c, int prec, int W, int rows, int band, int nframes, size_t npix, int max_steps, TraceArgs &T) {
+    if (!c->d_tr) HIPCHK(c, hipMalloc(&c->d_tr, 2 * TR_BYTES));
+    T = TraceArgs{};
+    T.pix_ctr = c->d_tr;
+    T.stats = reinterpret_cast<unsigned long long *>(c->d_tr + NR_MAX_QUEUES * 32);
+    T.nq_shift = c->nq_shift;
+    T.bw = (W + 7) / 8;
+    T.nblocks = T.bw * ((rows + 7) / 8);
+    const int sp = spread_for(c, prec, nframes, npix);
+    T.spread_shift = sp > 1 ? 31 - __builtin_clz((unsigned)sp) : 0;
+    T.inv_bw = 1.0 / (double)T.bw;
+    T.inv_band = 1.0 / (double)band;
+    T.eg_tau = endgame_tau(c, prec, max_steps);
+    T.x3lp_bytes = c->x3lp_bytes;
+    T.x3fl_bytes = c->x3fl_bytes;
+    return NR_OK;
+}
+
+// The grid of a launch of `total` pixels over `nframes` frames on `cus` CUs, and the rays per wave
+// that go with it (T.take, T.lane_cap).  T.eg_tau must be final: the endgame's instances have
+// their own workgroups per CU (trace_bpc).
+int trace_grid(const nr_ctx *c, int prec, TraceArgs &T, size_t total, int nframes, int cus) {
+    const int bpc = trace_bpc(c, prec, total, nframes, T.eg_tau > 0.0f && c->mlp16.x3n);
+    int grid = (int)std::min<size_t>((total + 255) / 256, (size_t)cus * bpc);
+    if (grid < 1) grid = 1;
+    T.take = wave_rays_for(c, prec, total, grid);
+    T.lane_cap = lane_cap_for(T.take);
+    return grid;
+}
+
+// Temporal block order (nr_set_temporal_order) around one launch: the launch dispenses the blocks
+// of its frames longest-first by the costs the previous launch of this frame-shard shape recorded
+// (the block layout is the same for every frame of a batch; the costs are the max over them), and
+// records its own for the next one.  order_buffers comes first.
+int order_begin(nr_ctx *c, TraceArgs &T, hipStream_t s) {
+    if (!c->temporal) return NR_OK;
+    T.order = c->order_valid ? c->d_order[c->order_cur] : nullptr;
+    T.bcost = c->d_bcost;
+    HIPCHK(c, hipMemsetAsync(c->d_bcost, 0, (size_t)T.nblocks * 4, s));
+    return NR_OK;
+}
+int order_end(nr_ctx *c, const TraceArgs &T, hipStream_t s) {
+    if (!c->temporal) return NR_OK;
+    HIPCHK(c, launch_order(c->d_bcost, c->d_order[c->order_cur ^ 1], T.nblocks, T.bw, c->temporal > 1, s));
+    c->order_cur ^= 1;
+    c->order_valid = 1;
+    return NR_OK;
+}
+
+// The statistics of a call's k_trace launches (T.stats, accumulated since the call cleared them)
+// and its ev0 -> ev1 time; without `stats` it only waits for results that went to the host.
+int trace_stats(nr_ctx *c, const TraceArgs &T, int launches, int loc, nr_stats *stats, hipStream_t s) {
+    unsigned long long hs[6];
+    if (stats) HIPCHK(c, hipMemcpyAsync(hs, T.stats, sizeof hs, hipMemcpyDeviceToHost, s));
+    float ms = 0;
+    const int rc = end_timed(c, stats != nullptr, loc, s, &ms);
+    if (rc != NR_OK || !stats) return rc;
+    nr_stats st{};
+    st.ray_steps = hs[0];
+    st.rays_hit = hs[1];
+    st.iterations = (int32_t)hs[2];
+    st.rays_shaded = hs[3];
+    st.shade_evals = 4ull * hs[3];
+    st.endgame_evals = hs[4];
+    st.endgame_switches = hs[5];
+    st.launches = launches;
+    st.ms_total = ms;
+    *stats = st;
+    return NR_OK;
+}
+
 // The MLP arguments of a launch over these frame numbers: the bf16 clamped-ReLU form
 // (nr_mlp16.h) needs every network input within LP_INPUT_BOUND.  Ray positions stay inside
 // the bounding sphere; the 4th input of an animation network is the frame number, checked here.
@@ -517,6 +689,9 @@ MlpArgs mlp_for_frames(const nr_ctx *c, const nr_frame *frames, int nframes, int
     return M;
 }
 
+// Per-frame arguments of a batch: pinned staging (reused only once the previous upload
+// has been consumed) + device copy.  With host outputs the frames of one launch go
+// through d_bout (`chunk` frames).
 int upload_frames(nr_ctx *c, const nr_frame *frames, int nframes, size_t npix, int loc, int chunk, hipStream_t s) {
     if (!c->ev_frames) HIPCHK(c, hipEventCreateWithFlags(&c->ev_frames, hipEventDisableTiming));
     HIPCHK(c, hipEventSynchronize(c->ev_frames));
@@ -567,7 +742,7 @@ int render_wavefront(nr_ctx *c, const nr_frame *frames, int nframes, int W, int 
     // counters: (max_steps + 1) x [WF_SEGS live counts], [WF_SEGS shade counts], then
     // max_steps shade flags; each count on its own 128-byte line
     const size_t line = (size_t)WF_SEGS * 32;
-    const float tau = endgame_tau(c, max_steps);
+    const float tau = endgame_tau(c, c->precision, max_steps);
     const bool eg = tau > 0.0f;
     // the endgame's counters after them: (max_steps + 1) x [WF_SEGS fine counts], then one switch
     // count per iteration
@@ -579,11 +754,7 @@ int render_wavefront(nr_ctx *c, const nr_frame *frames, int nframes, int W, int 
     if (eg && (rc = ensure_fine(c, seg_cap * WF_SEGS)) != NR_OK) return rc;
     if ((rc = ensure_ctr(c, nctr + 8)) != NR_OK) return rc;
     if ((rc = upload_frames(c, frames, nframes, npix, loc, chunk, s)) != NR_OK) return rc;
-    RenderArgs A{};
-    A.out = nullptr; A.W = W; A.H = H; A.rows = rows; A.band = band; A.nshards = nshards; A.shard = shard;
-    A.max_steps = max_steps; A.scene = c->scene; A.frame = 0; A.color_type = c->color_type;
-    A.matcap = c->d_matcap; A.mw = c->mw; A.mh = c->mh;
-    set_recips(A);
+    const RenderArgs A = render_args(c, W, H, rows, band, nshards, shard, max_steps);
     const int cus = num_cus(c->device);
     const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : 16;  // measured: 4 -> 2.10, 8 -> 2.06, 16 -> 2.02 ms/frame (32-frame batch)
     uint32_t *cnt = c->d_ctr, *shade_cnt = c->d_ctr + (size_t)(max_steps + 1) * line,
@@ -674,15 +845,8 @@ int render_wavefront(nr_ctx *c, const nr_frame *frames, int nframes, int W, int 
     }
     if (c->profiling) c->prof_renders += nframes;
     HIPCHK(c, hipEventRecord(c->ev1, s));
-    if (stats) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        tot.ms_total = ms;
-        *stats = tot;
-    } else if (loc != NR_DEVICE) {
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
+    if ((rc = end_timed(c, stats != nullptr, loc, s, &tot.ms_total)) != NR_OK) return rc;
+    if (stats) *stats = tot;
     return NR_OK;
 }
 
@@ -840,6 +1004,105 @@ int render_layered(nr_ctx *c, const RenderArgs &A0, uint32_t *out, size_t npix, 
     return queue_stats(c, max_steps, launches, stats, s);
 }
 
+// the context's view (nr_set_view) as a frame into `out`
+nr_frame context_view(const nr_ctx *c, uint32_t *out) {
+    nr_frame v;
+    memcpy(v.inv_view, c->inv_view, sizeof v.inv_view);
+    memcpy(v.normal, c->normal, sizeof v.normal);
+    v.frame = c->frame;
+    v.out = out;
+    return v;
+}
+
+// One frame (shard) of the view `v` into v.out, at precision `prec` on schedule `sched`:
+// nr_render_shard with what it takes from the context passed in, so that nr_render_batch's
+// frame-by-frame fallback and nr_render_aa's base frame render theirs without touching the context.
+int render_frame(nr_ctx *c, const nr_frame &v, int prec, int sched, int W, int H, int band, int nshards, int shard,
+                 int max_steps, int loc, nr_stats *stats) {
+    int rc;
+    if ((rc = check_shape(c, W, H, band, nshards, shard, max_steps)) != NR_OK) return rc;
+    if ((rc = check_scene(c)) != NR_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int rows = nr_shard_rows(H, band, nshards, shard);
+    const size_t npix = (size_t)W * rows;
+    if (npix == 0) { if (stats) *stats = nr_stats{}; return NR_OK; }
+    if ((rc = ensure_rays(c, npix)) != NR_OK) return rc;
+    if ((rc = ensure_ctr(c, (size_t)2 * max_steps + 8)) != NR_OK) return rc;
+    uint32_t *dout = v.out;
+    if (loc != NR_DEVICE) {
+        if ((rc = ensure_buf(c, c->d_out, c->cap_out, npix)) != NR_OK) return rc;
+        dout = c->d_out;
+    }
+    RenderArgs A = render_args(c, W, H, rows, band, nshards, shard, max_steps);
+    A.out = dout;
+    A.frame = v.frame;
+    memcpy(A.inv_view, v.inv_view, sizeof A.inv_view);
+    memcpy(A.normal, v.normal, sizeof A.normal);
+    GET_STREAM(c, s);
+    const int cus = num_cus(c->device);
+    if (!c->fused || sched == NR_SCHED_LAYERED) return render_layered(c, A, v.out, npix, max_steps, loc, stats, s);
+    if (sched != NR_SCHED_PERSISTENT) {
+        // the wavefront schedule (render_wavefront) on this one frame
+        nr_frame fr = v;
+        fr.out = dout;
+        if ((rc = render_wavefront(c, &fr, 1, W, H, band, nshards, shard, max_steps, NR_DEVICE, stats, s)) != NR_OK)
+            return rc;
+        if (loc != NR_DEVICE) {
+            HIPCHK(c, hipMemcpyAsync(v.out, dout, npix * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+        }
+        return NR_OK;
+    }
+    TraceArgs T;
+    if ((rc = trace_args(c, prec, W, rows, band, 1, npix, max_steps, T)) != NR_OK) return rc;
+    T.itmap = (c->debug & 8) != 0;
+    if (c->debug & 1) T.eg_tau = 0.0f;  // the stamps instance (nr_set_debug bit 0) marches without the endgame
+    if (c->temporal || c->probe_steps > 0)
+        if ((rc = order_buffers(c, W, H, band, nshards, shard, T.nblocks)) != NR_OK) return rc;
+    const bool probe = c->probe_steps > 0 && max_steps > 0 && !(c->temporal && c->order_valid);
+    const int grid = trace_grid(c, prec, T, npix, 1, cus);
+    if (c->debug & 1) {
+        if (!c->d_stamps) HIPCHK(c, hipMalloc(&c->d_stamps, (size_t)cus * 16 * 4 * 16 * 8));
+        T.stamps = c->d_stamps;
+        c->n_stamps = (size_t)grid * 4;
+    }
+    const MlpArgs M = mlp_for_frames(c, nullptr, 0, A.frame);
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, hipMemsetAsync(c->d_tr, 0, (probe ? 2 : 1) * TR_BYTES, s));
+    if (probe) {
+        // cost probe: march each block's centre ray for at most probe_steps iterations,
+        // then hand the blocks out longest-first
+        if ((rc = prof_begin(c, 0, s)) != NR_OK) return rc;
+        HIPCHK(c, hipMemsetAsync(c->d_bcost, 0, (size_t)T.nblocks * 4, s));
+        TraceArgs P = T;
+        P.probe = 1;
+        P.take = c->probe_take;
+        P.lane_cap = lane_cap_for(P.take);
+        P.pix_ctr = c->d_tr + TR_BYTES / 4;
+        P.stats = reinterpret_cast<unsigned long long *>(c->d_tr + TR_BYTES / 4 + NR_MAX_QUEUES * 32);
+        P.stamps = nullptr;
+        P.bcost = c->d_bcost;
+        P.spread_shift = 0;
+        RenderArgs Ap = A;
+        Ap.max_steps = std::min(max_steps, c->probe_steps);
+        const long pwaves = ((long)T.nblocks + P.take - 1) / P.take;
+        const int pgrid = (int)std::max<long>(1, std::min<long>((pwaves + 3) / 4, grid));
+        HIPCHK(c, launch_trace(Ap, M, P, prec, pgrid, s));
+        HIPCHK(c, launch_order(c->d_bcost, c->d_order[c->order_cur], T.nblocks, T.bw, c->probe_dilate, s));
+        if ((rc = prof_end(c, s)) != NR_OK) return rc;
+    }
+    if ((rc = order_begin(c, T, s)) != NR_OK) return rc;
+    if (probe) T.order = c->d_order[c->order_cur];  // (no recorded order: the probe's)
+    if ((rc = prof_begin(c, 1, s)) != NR_OK) return rc;
+    HIPCHK(c, launch_trace(A, M, T, prec, grid, s));
+    if ((rc = prof_end(c, s)) != NR_OK) return rc;
+    if ((rc = order_end(c, T, s)) != NR_OK) return rc;
+    if (c->profiling) c->prof_renders++;
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (loc != NR_DEVICE) HIPCHK(c, hipMemcpyAsync(v.out, dout, npix * 4, hipMemcpyDeviceToHost, s));
+    return trace_stats(c, T, 2, loc, stats, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -847,25 +1110,6 @@ extern "C" {
 int nr_abi_version(void) { return NR_ABI_VERSION; }
 
 const char *nr_last_error(const nr_ctx *ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
-
-// The context's stream: the caller's (nr_set_stream) or the private one, created here on
-// first use.  Returns NULL only if that creation failed (error recorded).
-#define GET_STREAM(c, s)                                           \
-    hipStream_t s = cur_stream(c);                                 \
-    if ((c)->use_own && !(c)->own_stream) return NR_E_HIP;
-
-static hipStream_t cur_stream(nr_ctx *c) {
-    if (c->use_own && !c->own_stream) {
-        if (hipSetDevice(c->device) != hipSuccess ||
-            hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
-            c->own_stream = nullptr;
-            set_err(c, NR_E_HIP, "stream creation failed");
-            return nullptr;
-        }
-        c->stream = c->own_stream;
-    }
-    return c->stream;
-}
 
 int nr_create(int device, nr_ctx **out) {
     if (!out) return set_err(nullptr, NR_E_INVALID, "nr_create: out is NULL");
@@ -1015,89 +1259,47 @@ int nr_render_batch(nr_ctx *c, const nr_frame *frames, int nframes, int W, int H
     if (!c || !frames || nframes < 1) return set_err(c, NR_E_INVALID, "nr_render_batch: bad arguments");
     for (int i = 0; i < nframes; ++i)
         if (!frames[i].out) return set_err(c, NR_E_INVALID, "nr_render_batch: frame %d has no output", i);
-    if (W < 1 || H < 1 || (long)W * H > (1l << 31)) return set_err(c, NR_E_INVALID, "nr_render: bad size %dx%d", W, H);
-    if (band < 1 || nshards < 1 || shard < 0 || shard >= nshards) return set_err(c, NR_E_INVALID, "nr_render: bad shard");
-    if (max_steps < 0) return set_err(c, NR_E_INVALID, "nr_render: max_steps < 0");
-    if (c->schedule == NR_SCHED_WAVEFRONT && c->fused) {
-        if (c->dims[0] != c->num_inputs)
-            return set_err(c, NR_E_STATE, "nr_render: network takes %d inputs but numInputs = %d", c->dims[0], c->num_inputs);
-        if (c->color_type == NR_COLOR_MATCAP && !c->d_matcap) return set_err(c, NR_E_STATE, "nr_render: matcap colouring without a matcap");
-        HIPCHK(c, hipSetDevice(c->device));
-        GET_STREAM(c, s);
-        return render_wavefront(c, frames, nframes, W, H, band, nshards, shard, max_steps, loc, stats, s);
-    }
-    if (c->schedule != NR_SCHED_PERSISTENT || !c->fused || (c->debug & (1 | 8))) {
-        // frame by frame (the wavefront and layered schedules and the diagnostics are
-        // single-frame)
-        float iv[12], nm[16];
-        memcpy(iv, c->inv_view, sizeof iv);
-        memcpy(nm, c->normal, sizeof nm);
-        const int fr0 = c->frame;
+    int rc;
+    if ((rc = check_shape(c, W, H, band, nshards, shard, max_steps)) != NR_OK) return rc;
+    const bool wavefront = c->schedule == NR_SCHED_WAVEFRONT && c->fused;
+    if (!wavefront && (c->schedule != NR_SCHED_PERSISTENT || !c->fused || (c->debug & (1 | 8)))) {
+        // frame by frame (the layered schedule, a network the fused kernels do not take and the
+        // diagnostics are single-frame)
         nr_stats tot{};
-        int rc = NR_OK;
-        for (int i = 0; i < nframes && rc == NR_OK; ++i) {
-            memcpy(c->inv_view, frames[i].inv_view, sizeof iv);
-            memcpy(c->normal, frames[i].normal, sizeof nm);
-            c->frame = frames[i].frame;
+        for (int i = 0; i < nframes; ++i) {
             nr_stats st{};
-            rc = nr_render_shard(c, frames[i].out, W, H, band, nshards, shard, max_steps, loc, stats ? &st : nullptr);
+            rc = render_frame(c, frames[i], c->precision, c->schedule, W, H, band, nshards, shard, max_steps, loc,
+                              stats ? &st : nullptr);
+            if (rc != NR_OK) return rc;
             tot.ray_steps += st.ray_steps; tot.shade_evals += st.shade_evals; tot.rays_hit += st.rays_hit;
             tot.rays_shaded += st.rays_shaded; tot.iterations = std::max(tot.iterations, st.iterations);
             tot.launches += st.launches; tot.ms_total += st.ms_total; tot.endgame_evals += st.endgame_evals;
             tot.endgame_switches += st.endgame_switches;
         }
-        memcpy(c->inv_view, iv, sizeof iv);
-        memcpy(c->normal, nm, sizeof nm);
-        c->frame = fr0;
-        if (rc == NR_OK && stats) *stats = tot;
-        return rc;
+        if (stats) *stats = tot;
+        return NR_OK;
     }
-    if (c->dims.empty()) return set_err(c, NR_E_STATE, "nr_render: no network loaded");
-    if (!c->fused)
-        return set_err(c, NR_E_FORMAT, "nr_render: network shape unsupported by the fused march kernel "
-                                       "(needs [3|4, 32, ..., 32, 1])");
-    if (c->dims[0] != c->num_inputs)
-        return set_err(c, NR_E_STATE, "nr_render: network takes %d inputs but numInputs = %d", c->dims[0], c->num_inputs);
-    if (c->color_type == NR_COLOR_MATCAP && !c->d_matcap) return set_err(c, NR_E_STATE, "nr_render: matcap colouring without a matcap");
+    if ((rc = check_scene(c)) != NR_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
+    if (wavefront) {
+        GET_STREAM(c, s);
+        return render_wavefront(c, frames, nframes, W, H, band, nshards, shard, max_steps, loc, stats, s);
+    }
     const int rows = nr_shard_rows(H, band, nshards, shard);
     const size_t npix = (size_t)W * rows;
-    nr_stats st{};
-    if (npix == 0) { if (stats) *stats = st; return NR_OK; }
+    if (npix == 0) { if (stats) *stats = nr_stats{}; return NR_OK; }
     GET_STREAM(c, s);
-    int rc;
     const int chunk = nr_batch_frames_per_launch(W, H, band, nshards, shard, nframes, 1 << c->nq_shift);
     if (chunk < 1)
         return set_err(c, NR_E_INVALID, "nr_render_batch: %dx%d shard overflows the 32-bit pixel queue", W, H);
     if ((rc = upload_frames(c, frames, nframes, npix, loc, chunk, s)) != NR_OK) return rc;
-
-    RenderArgs A{};
-    A.out = nullptr; A.W = W; A.H = H; A.rows = rows; A.band = band; A.nshards = nshards; A.shard = shard;
-    A.max_steps = max_steps; A.scene = c->scene; A.frame = 0; A.color_type = c->color_type;
-    A.matcap = c->d_matcap; A.mw = c->mw; A.mh = c->mh;
-    set_recips(A);
-    const size_t tr_bytes = NR_MAX_QUEUES * 128 + 8 * 8;
-    if (!c->d_tr) HIPCHK(c, hipMalloc(&c->d_tr, 2 * tr_bytes));
-    TraceArgs T{};
-    T.pix_ctr = c->d_tr;
-    T.stats = reinterpret_cast<unsigned long long *>(c->d_tr + NR_MAX_QUEUES * 32);
-    T.nq_shift = c->nq_shift;
-    T.bw = (W + 7) / 8;
-    T.nblocks = T.bw * ((rows + 7) / 8);
-    {
-        const int sp = spread_for(c, nframes, npix);
-        T.spread_shift = sp > 1 ? 31 - __builtin_clz((unsigned)sp) : 0;
-    }
-    T.inv_bw = 1.0 / (double)T.bw;
-    T.inv_band = 1.0 / (double)band;
+    // out, frame and the view stay clear: the frames' are in their FrameArgs
+    const RenderArgs A = render_args(c, W, H, rows, band, nshards, shard, max_steps);
+    const MlpArgs M = mlp_for_frames(c, frames, nframes, 0);
+    TraceArgs T;
+    if ((rc = trace_args(c, c->precision, W, rows, band, nframes, npix, max_steps, T)) != NR_OK) return rc;
     const int cus = num_cus(c->device);
-    // temporal block order (nr_set_temporal_order): every launch dispenses the blocks of its
-    // frames longest-first by the costs the previous launch of this frame-shard shape recorded
-    // (the block layout is the same for every frame of a batch; the costs are the max over them)
-    if (c->temporal) {
-        int rc3;
-        if ((rc3 = order_buffers(c, W, H, band, nshards, shard, T.nblocks)) != NR_OK) return rc3;
-    }
+    if (c->temporal && (rc = order_buffers(c, W, H, band, nshards, shard, T.nblocks)) != NR_OK) return rc;
     HIPCHK(c, hipEventRecord(c->ev0, s));
     int launches = 0;
     for (int f0 = 0; f0 < nframes; f0 += chunk) {
@@ -1110,32 +1312,16 @@ int nr_render_batch(nr_ctx *c, const nr_frame *frames, int nframes, int W, int H
         // (1024^2 x 32 frames 1.866 -> 1.825 ms/frame, one 8-way shard x 8 frames 0.367 ->
         // 0.334; profiles/r2_ab_experiments.txt (10)).  Debug bit 10: frame-major (A/B).
         T.interleave = !((c->debug >> 10) & 1);
-        T.eg_tau = endgame_tau(c, max_steps);
-        T.x3lp_bytes = c->x3lp_bytes;
-        T.x3fl_bytes = c->x3fl_bytes;
         // the counters restart for every launch; the statistics accumulate
-        HIPCHK(c, hipMemsetAsync(c->d_tr, 0, f0 == 0 ? tr_bytes : (size_t)NR_MAX_QUEUES * 128, s));
+        HIPCHK(c, hipMemsetAsync(c->d_tr, 0, f0 == 0 ? TR_BYTES : (size_t)NR_MAX_QUEUES * 128, s));
         // workgroups per CU: default_bpc (with several frames in a launch their tails overlap,
         // so the extra waves per SIMD lift the bulk rate instead of lengthening the tail)
-        const int bpc = trace_bpc(c, npix * n, n, T.eg_tau > 0.0f && c->mlp16.x3n);
-        int grid = (int)std::min<size_t>((npix * n + 255) / 256, (size_t)cus * bpc);
-        if (grid < 1) grid = 1;
-        T.take = wave_rays_for(c, npix * n, grid);
-        T.lane_cap = T.take >= 64 ? ~0ull : (1ull << T.take) - 1ull;
-        if (c->temporal) {
-            T.order = c->order_valid ? c->d_order[c->order_cur] : nullptr;
-            T.bcost = c->d_bcost;
-            HIPCHK(c, hipMemsetAsync(c->d_bcost, 0, (size_t)T.nblocks * 4, s));
-        }
-        int rc2;
-        if ((rc2 = prof_begin(c, 1, s)) != NR_OK) return rc2;
-        HIPCHK(c, launch_trace(A, mlp_for_frames(c, frames, nframes, 0), T, c->precision, grid, s));
-        if ((rc2 = prof_end(c, s)) != NR_OK) return rc2;
-        if (c->temporal) {  // the order for the next launch of this shape
-            HIPCHK(c, launch_order(c->d_bcost, c->d_order[c->order_cur ^ 1], T.nblocks, T.bw, c->temporal > 1, s));
-            c->order_cur ^= 1;
-            c->order_valid = 1;
-        }
+        const int grid = trace_grid(c, c->precision, T, npix * n, n, cus);
+        if ((rc = order_begin(c, T, s)) != NR_OK) return rc;
+        if ((rc = prof_begin(c, 1, s)) != NR_OK) return rc;
+        HIPCHK(c, launch_trace(A, M, T, c->precision, grid, s));
+        if ((rc = prof_end(c, s)) != NR_OK) return rc;
+        if ((rc = order_end(c, T, s)) != NR_OK) return rc;
         ++launches;
         if (loc != NR_DEVICE)
             for (int i = f0; i < f0 + n; ++i)
@@ -1144,205 +1330,14 @@ int nr_render_batch(nr_ctx *c, const nr_frame *frames, int nframes, int W, int H
     }
     if (c->profiling) c->prof_renders += nframes;
     HIPCHK(c, hipEventRecord(c->ev1, s));
-    if (stats) {
-        unsigned long long hs[6];
-        HIPCHK(c, hipMemcpyAsync(hs, T.stats, sizeof hs, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        st.ray_steps = hs[0];
-        st.endgame_evals = hs[4];
-        st.endgame_switches = hs[5];
-        st.rays_hit = hs[1];
-        st.iterations = (int32_t)hs[2];
-        st.rays_shaded = hs[3];
-        st.shade_evals = 4ull * hs[3];
-        st.launches = launches;
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        st.ms_total = ms;
-        *stats = st;
-    } else if (loc != NR_DEVICE) {
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
-    return NR_OK;
-}
-
-// Queue positions are uint32 (pix_ctr atomics in k_trace): one launch hands out
-// shard_total = blocks of the busiest queue shard x 64 x frames positions.  Past a shard's end
-// a wave of the low-precision tracers can take two pending reservations of up to 64 positions
-// (NR_QUEUE_CHUNK_DENSE: one absorbed and found past the end while the wave still had positions
-// of its pool, the next requested right after) and one blocking reservation of up to 64 before
-// it moves on: with the grid nr_set_occupancy allows (16 workgroups x 4 waves per CU) on up to
-// 512 CUs the over-reservation stays below 512 x 16 x 4 x 192 = 6,291,456 (ADVICE r2: the old
-// 2^19 assumed 8 workgroups and no pending reservation).
-int nr_batch_frames_per_launch(int W, int H, int band, int nshards, int shard, int nframes, int queue_shards) {
-    if (W < 1 || H < 1 || nframes < 1 || queue_shards < 1) return 0;
-    const int rows = nr_shard_rows(H, band, nshards, shard);
-    if (rows < 1) return std::min(nframes, NR_MAX_BATCH);
-    const long long nblocks = (long long)((W + 7) / 8) * ((rows + 7) / 8);
-    const long long per_frame = ((nblocks + queue_shards - 1) / queue_shards) * 64;  // busiest shard
-    const long long slop = 512ll * 16 * 4 * (64 + 2 * 64);
-    const long long cap = ((1ll << 32) - 1 - slop) / per_frame;
-    return (int)std::min<long long>(std::min(nframes, NR_MAX_BATCH), cap);
-}
-
-int nr_shard_rows(int H, int band, int nshards, int shard) {
-    if (H < 0 || band < 1 || nshards < 1 || shard < 0 || shard >= nshards) return 0;
-    int full = H / band, rem = H % band;
-    int rows = (full / nshards) * band;
-    int extra = full % nshards;               // bands beyond the complete rounds
-    if (shard < extra) rows += band;
-    if (shard == extra && rem) rows += rem;   // the partial last band
-    return rows;
+    return trace_stats(c, T, launches, loc, stats, s);
 }
 
 int nr_render_shard(nr_ctx *c, uint32_t *out, int W, int H, int band, int nshards, int shard, int max_steps, int loc,
                     nr_stats *stats) {
     if (!c || !out) return set_err(c, NR_E_INVALID, "nr_render: NULL argument");
-    if (W < 1 || H < 1 || (long)W * H > (1l << 31)) return set_err(c, NR_E_INVALID, "nr_render: bad size %dx%d", W, H);
-    if (band < 1 || nshards < 1 || shard < 0 || shard >= nshards) return set_err(c, NR_E_INVALID, "nr_render: bad shard");
-    if (max_steps < 0) return set_err(c, NR_E_INVALID, "nr_render: max_steps < 0");
-    if (c->dims.empty()) return set_err(c, NR_E_STATE, "nr_render: no network loaded");
-    if (c->dims.back() != 1)
-        return set_err(c, NR_E_FORMAT, "nr_render: the SDF network must have one output (has %d)", c->dims.back());
-    if (c->dims[0] != c->num_inputs)
-        return set_err(c, NR_E_STATE, "nr_render: network takes %d inputs but numInputs = %d", c->dims[0], c->num_inputs);
-    if (c->color_type == NR_COLOR_MATCAP && !c->d_matcap) return set_err(c, NR_E_STATE, "nr_render: matcap colouring without a matcap");
-    HIPCHK(c, hipSetDevice(c->device));
-    int rows = nr_shard_rows(H, band, nshards, shard);
-    size_t npix = (size_t)W * rows;
-    nr_stats st{};
-    if (npix == 0) { if (stats) *stats = st; return NR_OK; }
-    int rc;
-    if ((rc = ensure_rays(c, npix)) != NR_OK) return rc;
-    if ((rc = ensure_ctr(c, (size_t)2 * max_steps + 8)) != NR_OK) return rc;
-    uint32_t *dout = out;
-    if (loc != NR_DEVICE) {
-        if ((rc = ensure_buf(c, c->d_out, c->cap_out, npix)) != NR_OK) return rc;
-        dout = c->d_out;
-    }
-    RenderArgs A{};
-    A.out = dout; A.W = W; A.H = H; A.rows = rows; A.band = band; A.nshards = nshards; A.shard = shard;
-    A.max_steps = max_steps; A.scene = c->scene; A.frame = c->frame; A.color_type = c->color_type;
-    A.matcap = c->d_matcap; A.mw = c->mw; A.mh = c->mh;
-    set_recips(A);
-    memcpy(A.inv_view, c->inv_view, sizeof A.inv_view);
-    memcpy(A.normal, c->normal, sizeof A.normal);
-    GET_STREAM(c, s);
-    int cus = num_cus(c->device);
-    int rc2;
-    if (!c->fused || c->schedule == NR_SCHED_LAYERED) return render_layered(c, A, out, npix, max_steps, loc, stats, s);
-    if (c->schedule == NR_SCHED_PERSISTENT) {
-        // 8 shard counters on their own 128-byte lines, then 4 x u64 stats
-        // (a second set for the cost probe)
-        const size_t tr_bytes = NR_MAX_QUEUES * 128 + 8 * 8;
-        if (!c->d_tr) HIPCHK(c, hipMalloc(&c->d_tr, 2 * tr_bytes));
-        TraceArgs T{};
-        T.pix_ctr = c->d_tr;
-        T.stats = reinterpret_cast<unsigned long long *>(c->d_tr + NR_MAX_QUEUES * 32);
-        T.nq_shift = c->nq_shift;
-        const int bw = (W + 7) / 8, bh = (rows + 7) / 8;
-        T.bw = bw;
-        T.nblocks = bw * bh;
-        T.itmap = (c->debug & 8) != 0;
-        // the stamps instance (nr_set_debug bit 0) marches without the endgame
-        T.eg_tau = (c->debug & 1) ? 0.0f : endgame_tau(c, max_steps);
-        T.x3lp_bytes = c->x3lp_bytes;
-        T.x3fl_bytes = c->x3fl_bytes;
-        {
-            const int sp = spread_for(c, 1, npix);
-            T.spread_shift = sp > 1 ? 31 - __builtin_clz((unsigned)sp) : 0;
-        }
-        T.inv_bw = 1.0 / (double)T.bw;
-        T.inv_band = 1.0 / (double)band;
-        if (c->temporal || c->probe_steps > 0)
-            if ((rc2 = order_buffers(c, W, H, band, nshards, shard, T.nblocks)) != NR_OK) return rc2;
-        const bool probe = c->probe_steps > 0 && max_steps > 0 && !(c->temporal && c->order_valid);
-        if (c->temporal) {
-            T.order = c->order_valid ? c->d_order[c->order_cur] : nullptr;
-            T.bcost = c->d_bcost;
-        }
-        const int bpc = trace_bpc(c, npix, 1, T.eg_tau > 0.0f && c->mlp16.x3n);
-        int grid = (int)std::min<size_t>((npix + 255) / 256, (size_t)cus * bpc);
-        if (grid < 1) grid = 1;
-        T.take = wave_rays_for(c, npix, grid);
-        T.lane_cap = T.take >= 64 ? ~0ull : (1ull << T.take) - 1ull;
-        if (c->debug & 1) {
-            if (!c->d_stamps) HIPCHK(c, hipMalloc(&c->d_stamps, (size_t)cus * 16 * 4 * 16 * 8));
-            T.stamps = c->d_stamps;
-            c->n_stamps = (size_t)grid * 4;
-        }
-        HIPCHK(c, hipEventRecord(c->ev0, s));
-        HIPCHK(c, hipMemsetAsync(c->d_tr, 0, (probe ? 2 : 1) * tr_bytes, s));
-        if (probe) {
-            // cost probe: march each block's centre ray for at most probe_steps iterations,
-            // then hand the blocks out longest-first
-            if ((rc2 = prof_begin(c, 0, s)) != NR_OK) return rc2;
-            HIPCHK(c, hipMemsetAsync(c->d_bcost, 0, (size_t)T.nblocks * 4, s));
-            TraceArgs P = T;
-            P.probe = 1;
-            P.take = c->probe_take;
-            P.lane_cap = P.take >= 64 ? ~0ull : (1ull << P.take) - 1ull;
-            P.pix_ctr = c->d_tr + tr_bytes / 4;
-            P.stats = reinterpret_cast<unsigned long long *>(c->d_tr + tr_bytes / 4 + NR_MAX_QUEUES * 32);
-            P.stamps = nullptr;
-            P.order = nullptr;
-            P.bcost = c->d_bcost;
-            P.spread_shift = 0;
-            RenderArgs Ap = A;
-            Ap.max_steps = std::min(max_steps, c->probe_steps);
-            const long pwaves = ((long)T.nblocks + P.take - 1) / P.take;
-            const int pgrid = (int)std::max<long>(1, std::min<long>((pwaves + 3) / 4, grid));
-            HIPCHK(c, launch_trace(Ap, mlp_for_frames(c, nullptr, 0, A.frame), P, c->precision, pgrid, s));
-            HIPCHK(c, launch_order(c->d_bcost, c->d_order[c->order_cur], T.nblocks, T.bw, c->probe_dilate, s));
-            if ((rc2 = prof_end(c, s)) != NR_OK) return rc2;
-            T.order = c->d_order[c->order_cur];
-        }
-        if (T.bcost) HIPCHK(c, hipMemsetAsync(c->d_bcost, 0, (size_t)T.nblocks * 4, s));
-        if ((rc2 = prof_begin(c, 1, s)) != NR_OK) return rc2;
-        HIPCHK(c, launch_trace(A, mlp_for_frames(c, nullptr, 0, A.frame), T, c->precision, grid, s));
-        if ((rc2 = prof_end(c, s)) != NR_OK) return rc2;
-        if (c->temporal) {  // order for the next frame of the same configuration
-            HIPCHK(c, launch_order(c->d_bcost, c->d_order[c->order_cur ^ 1], T.nblocks, T.bw, c->temporal > 1, s));
-            c->order_cur ^= 1;
-            c->order_valid = 1;
-        }
-        if (c->profiling) c->prof_renders++;
-        HIPCHK(c, hipEventRecord(c->ev1, s));
-        if (loc != NR_DEVICE) HIPCHK(c, hipMemcpyAsync(out, dout, npix * 4, hipMemcpyDeviceToHost, s));
-        if (stats) {
-            unsigned long long hs[6];
-            HIPCHK(c, hipMemcpyAsync(hs, T.stats, sizeof hs, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipStreamSynchronize(s));
-            st.ray_steps = hs[0];
-            st.endgame_evals = hs[4];
-            st.endgame_switches = hs[5];
-            st.rays_hit = hs[1];
-            st.iterations = (int32_t)hs[2];
-            st.rays_shaded = hs[3];
-            st.shade_evals = 4ull * hs[3];
-            st.launches = 2;
-            float ms = 0;
-            HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-            st.ms_total = ms;
-            *stats = st;
-        } else if (loc != NR_DEVICE) {
-            HIPCHK(c, hipStreamSynchronize(s));
-        }
-        return NR_OK;
-    }
-    // ---- wavefront schedule (render_wavefront) on this one frame
-    nr_frame fr{};
-    memcpy(fr.inv_view, c->inv_view, sizeof fr.inv_view);
-    memcpy(fr.normal, c->normal, sizeof fr.normal);
-    fr.frame = c->frame;
-    fr.out = dout;
-    if ((rc2 = render_wavefront(c, &fr, 1, W, H, band, nshards, shard, max_steps, NR_DEVICE, stats, s)) != NR_OK)
-        return rc2;
-    if (loc != NR_DEVICE) {
-        HIPCHK(c, hipMemcpyAsync(out, dout, npix * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
-    return NR_OK;
+    return render_frame(c, context_view(c, out), c->precision, c->schedule, W, H, band, nshards, shard, max_steps, loc,
+                        stats);
 }
 
 int nr_render(nr_ctx *c, uint32_t *out, int W, int H, int max_steps, int loc, nr_stats *stats) {
@@ -1407,23 +1402,17 @@ static int query_rays(nr_ctx *c, const char *fn, const float *origins, const flo
         if (position) HIPCHK(c, hipMemcpyAsync(position, Q.position, 3 * N * 4, hipMemcpyDeviceToHost, s));
         if (normal) HIPCHK(c, hipMemcpyAsync(normal, Q.normal, 3 * N * 4, hipMemcpyDeviceToHost, s));
     }
-    if (stats) {
-        unsigned long long hs[4];
-        HIPCHK(c, hipMemcpyAsync(hs, Q.stats, sizeof hs, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        st.ray_steps = hs[0];
-        st.rays_hit = hs[1];
-        st.iterations = (int32_t)hs[2];
-        st.rays_shaded = hs[3];
-        st.shade_evals = normal ? 4ull * hs[3] : 0ull;
-        st.launches = 2;
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        st.ms_total = ms;
-        *stats = st;
-    } else if (loc != NR_DEVICE) {
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
+    unsigned long long hs[4];
+    if (stats) HIPCHK(c, hipMemcpyAsync(hs, Q.stats, sizeof hs, hipMemcpyDeviceToHost, s));
+    const int rc = end_timed(c, stats != nullptr, loc, s, &st.ms_total);
+    if (rc != NR_OK || !stats) return rc;
+    st.ray_steps = hs[0];
+    st.rays_hit = hs[1];
+    st.iterations = (int32_t)hs[2];
+    st.rays_shaded = hs[3];
+    st.shade_evals = normal ? 4ull * hs[3] : 0ull;
+    st.launches = 2;
+    *stats = st;
     return NR_OK;
 }
 
@@ -1474,17 +1463,11 @@ int nr_render_aa(nr_ctx *c, uint32_t *out, int W, int H, int samples, int mode, 
         if ((rc = ensure_buf(c, c->d_out, c->cap_out, npix)) != NR_OK) return rc;
         dout = c->d_out;
     }
-    // ---- the base frame: always the fp32 persistent tracer, the context's settings put back after it
+    // ---- the base frame: always the fp32 persistent tracer, whatever the context's settings
     nr_stats st{};
-    {
-        const int prec = c->precision, sched = c->schedule;
-        c->precision = NR_PRECISION_FP32;
-        c->schedule = NR_SCHED_PERSISTENT;
-        rc = nr_render_shard(c, dout, W, H, H, 1, 0, max_steps, NR_DEVICE, stats ? &st : nullptr);
-        c->precision = prec;
-        c->schedule = sched;
-        if (rc != NR_OK) return rc;
-    }
+    rc = render_frame(c, context_view(c, dout), NR_PRECISION_FP32, NR_SCHED_PERSISTENT, W, H, H, 1, 0, max_steps, NR_DEVICE,
+                      stats ? &st : nullptr);
+    if (rc != NR_OK) return rc;
     const int S = samples;
     const bool full = mode == NR_AA_FULL;
     long nedge = 0;
@@ -1518,11 +1501,8 @@ int nr_render_aa(nr_ctx *c, uint32_t *out, int W, int H, int samples, int mode, 
             X.inv_nedge = 1.0 / (double)cnt;
             X.nsub = cnt * (uint32_t)X.per;  // < S W * S H <= 2^30
             // the S W x S H frame's arguments, as nr_render builds them
-            RenderArgs A{};
-            A.out = nullptr; A.W = S * W; A.H = S * H; A.rows = A.H; A.band = A.H; A.nshards = 1; A.shard = 0;
-            A.max_steps = max_steps; A.scene = c->scene; A.frame = c->frame; A.color_type = c->color_type;
-            A.matcap = c->d_matcap; A.mw = c->mw; A.mh = c->mh;
-            set_recips(A);
+            RenderArgs A = render_args(c, S * W, S * H, S * H, S * H, 1, 0, max_steps);
+            A.frame = c->frame;
             memcpy(A.inv_view, c->inv_view, sizeof A.inv_view);
             memcpy(A.normal, c->normal, sizeof A.normal);
             // The grid by the CU count (nr_set_occupancy's workgroups per CU, or AA_BPC), at least 16
@@ -1694,18 +1674,11 @@ int nr_sample_grid(nr_ctx *c, const float origin[3], const float step[3], const 
     if ((rc = grid_launch(c, L, d, s)) != NR_OK) return rc;
     HIPCHK(c, hipEventRecord(c->ev1, s));
     if (loc != NR_DEVICE) HIPCHK(c, hipMemcpyAsync(sdf, d, N * 4, hipMemcpyDeviceToHost, s));
-    if (stats) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        nr_stats st{};
-        st.ray_steps = N;
-        st.launches = 1;
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        st.ms_total = ms;
-        *stats = st;
-    } else if (loc != NR_DEVICE) {
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
+    nr_stats st{};
+    st.ray_steps = N;
+    st.launches = 1;
+    if ((rc = end_timed(c, stats != nullptr, loc, s, &st.ms_total)) != NR_OK) return rc;
+    if (stats) *stats = st;
     return NR_OK;
 }
 
@@ -1970,18 +1943,11 @@ int nr_mlp_gradient(nr_ctx *c, const float *X, long n, float *value, float *grad
         if (grad) HIPCHK(c, hipMemcpyAsync(grad, G.grad, N * in0 * 4, hipMemcpyDeviceToHost, s));
         if (normal) HIPCHK(c, hipMemcpyAsync(normal, G.normal, 3 * N * 4, hipMemcpyDeviceToHost, s));
     }
-    if (stats) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        st.ray_steps = (uint64_t)n;
-        st.launches = 1;
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        st.ms_total = ms;
-        *stats = st;
-    } else if (loc != NR_DEVICE) {
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
-    return NR_OK;
+    st.ray_steps = (uint64_t)n;
+    st.launches = 1;
+    const int rc = end_timed(c, stats != nullptr, loc, s, &st.ms_total);
+    if (rc == NR_OK && stats) *stats = st;
+    return rc;
 }
 
 int nr_layer_forward(nr_ctx *c, int layer, const float *A, float *Z, long n, int loc) {

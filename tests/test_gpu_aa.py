@@ -286,6 +286,27 @@ def test_settings_ignored_and_preserved(rend):
     assert not np.array_equal(before, oracle_frame("close", W, H)[0])
 
 
+def test_aa_leaves_precision_and_schedule_alone(rend):
+    """In a bf16 context on the wavefront schedule the call gives the frame an fp32 persistent
+    context gives, and the context's own renders before and after it are the same frame."""
+    W, H, S, steps = 96, 77, 2, 64
+    setup(rend, "close")
+    ref, rst = rend.render_aa(W, H, S, "adaptive", 32, steps)
+    assert rst["edge_pixels"] >= 50
+    try:
+        rend.set_precision("bf16").set_schedule("wavefront")
+        before, bst = rend.render(W, H, steps)
+        img, st = rend.render_aa(W, H, S, "adaptive", 32, steps)
+        after, ast = rend.render(W, H, steps)
+    finally:
+        rend.set_precision("fp32").set_schedule("persistent")
+    assert_frame(after, before)
+    assert_frame(img, ref)
+    assert st["edge_pixels"] == rst["edge_pixels"]
+    for k in STAT_KEYS:
+        assert st[k] == rst[k] and ast[k] == bst[k], k
+
+
 def test_determinism_and_device_output(rend):
     """Two calls give the same bits; a device buffer on a caller-supplied stream holds what the host
     output holds."""

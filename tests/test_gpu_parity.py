@@ -395,6 +395,38 @@ def test_render_batch_matches_single_frames(rend, nets, chrome, nshards, shard, 
     rend.set_view(*nr.camera(0, 0, 2), 0)
 
 
+def test_fallback_batch_leaves_view_alone(rend, nets, chrome):
+    """nr_render_batch's frame-by-frame forms (the layered schedule; the persistent one with the
+    iteration map, debug bit 3) render each frame's own camera and leave the context's view as
+    it was: the next nr_render gives the frame it gave before them, bit for bit."""
+    dims, K, B = nets["plane_1"]
+    rend.load_mlp(dims, K, B).set_precision("fp32").set_static(nr.NR_COLOR_MATCAP, 3).set_scene("v1")
+    rend.set_matcap(chrome).set_schedule("persistent")
+    W, H, steps = 96, 77, 64
+    cams = [(*nr.camera(-20.0 + 15 * i, 50.0 + 100 * i, 2.0), 30 * (i + 1)) for i in range(3)]
+    modes = [("layered", 0), ("persistent", 8)]
+    try:
+        rend.set_view(*nr.camera(10.0, 200.0, 2.25), 5)
+        r0, s0 = rend.render(W, H, steps)
+        batches = []
+        for schedule, debug in modes:
+            rend.set_schedule(schedule).set_debug(debug)
+            batches.append(rend.render_batch(W, H, cams, steps, band=H))
+        rend.set_schedule("persistent").set_debug(0)
+        r1, s1 = rend.render(W, H, steps)
+        assert np.array_equal(r1, r0) and s1["ray_steps"] == s0["ray_steps"]
+        for (schedule, debug), (imgs, st) in zip(modes, batches):
+            rend.set_schedule(schedule).set_debug(debug)
+            tot = 0
+            for (iv, nm, fr), img in zip(cams, imgs):
+                ref, rst = rend.set_view(iv, nm, fr).render(W, H, steps)
+                assert np.array_equal(img, ref), (schedule, debug)
+                tot += rst["ray_steps"]
+            assert st["ray_steps"] == tot, (schedule, debug)
+    finally:
+        rend.set_schedule("persistent").set_debug(0).set_view(*nr.camera(0, 0, 2), 0)
+
+
 @pytest.mark.parametrize("prec,spread", [("fp32", 0), ("fp32", 16), ("bf16", -1), ("fp16", -1)])
 def test_render_batch_schedules_same_pixels(rend, nets, chrome, prec, spread):
     """Batched launches of >= 4 frames deal pixels block-major by default and, in bf16/fp16,
