@@ -38,7 +38,7 @@ EXPORTS = [
     "nr_h5_dims", "nr_h5_read_f32",
     "nr_group_create", "nr_group_destroy", "nr_group_size", "nr_group_render_batch", "nr_pack_x3",
     "nr_set_endgame", "nr_group_create_ex", "nr_group_synchronize", "nr_group_layout",
-    "nr_trace_rays", "nr_render_gbuffer", "nr_render_aa",
+    "nr_trace_rays", "nr_render_gbuffer", "nr_render_aa", "nr_render_lit",
     "nr_sample_grid", "nr_mesh_grid", "nr_extract_mesh", "nr_obj_save",
     "nr_mlp_gradient",
     "nr_pack_fp32_pruned", "nr_set_prune", "nr_prune_info", "nr_prune_redos",
@@ -69,6 +69,19 @@ class NRFrame(ctypes.Structure):
         ("normal", ctypes.c_float * 16),
         ("frame", ctypes.c_int),
         ("out", ctypes.c_void_p),
+    ]
+
+
+class NRLight(ctypes.Structure):
+    """nr_light: the directional light of nr_render_lit."""
+    _fields_ = [
+        ("dir", ctypes.c_float * 3),
+        ("shadow_steps", ctypes.c_int),
+        ("shadow_bias", ctypes.c_float),
+        ("shadow_k", ctypes.c_float),
+        ("ao_step", ctypes.c_float),
+        ("ao_strength", ctypes.c_float),
+        ("ambient", ctypes.c_float),
     ]
 
 
@@ -128,6 +141,7 @@ def lib():
         "nr_trace_rays": (I, [P, P, P, L64, I, P, P, P, P, P, I, ctypes.POINTER(NRStats)]),
         "nr_render_gbuffer": (I, [P, I, I, I, P, P, P, P, P, I, ctypes.POINTER(NRStats)]),
         "nr_render_aa": (I, [P, P, I, I, I, I, I, I, I, ctypes.POINTER(L64), ctypes.POINTER(NRStats)]),
+        "nr_render_lit": (I, [P, P, I, I, I, ctypes.POINTER(NRLight), P, P, I, ctypes.POINTER(NRStats)]),
         "nr_sample_grid": (I, [P, FP, FP, IP, P, I, ctypes.POINTER(NRStats)]),
         "nr_mesh_grid": (I, [P, P, FP, FP, IP, F, P, L64, P, L64, ctypes.POINTER(L64), ctypes.POINTER(L64), I]),
         "nr_extract_mesh": (I, [P, FP, FP, IP, F, P, P, L64, P, L64, ctypes.POINTER(L64), ctypes.POINTER(L64), I,

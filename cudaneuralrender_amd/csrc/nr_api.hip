@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -97,6 +98,14 @@ struct nr_ctx {
     size_t cap_aalist = 0;
     unsigned long long *d_aaacc = nullptr;
     size_t cap_aaacc = 0;
+    // lighting (nr_render_lit): the pixel cursor on its own 128-byte line + 4 x u64 stats; the
+    // geometry buffer (status, position, normal: 28 B per pixel) and the ao / shadow values the
+    // caller gave no device buffer for (8 B per pixel)
+    uint32_t *d_ls = nullptr;
+    float *d_lgbuf = nullptr;
+    size_t cap_lgbuf = 0;
+    float *d_lao = nullptr;
+    size_t cap_lao = 0;
     // volume sampling and isosurface extraction (nr_sample_grid, nr_mesh_grid, nr_extract_mesh):
     // the lattice of nr_extract_mesh (4 B per point; the staging of host lattices too), the
     // extraction's scratch (MeshArgs: 4 B per point + 24 B per 256 points) and the staging of
@@ -1142,6 +1151,7 @@ int nr_destroy(nr_ctx *c) {
     dfree(c->d_frames); dfree(c->d_bout);
     dfree(c->d_qs); dfree(c->d_qio);
     dfree(c->d_aas); dfree(c->d_aalist); dfree(c->d_aaacc);
+    dfree(c->d_ls); dfree(c->d_lgbuf); dfree(c->d_lao);
     dfree(c->d_grid); dfree(c->d_mesh); dfree(c->d_mio);
     if (c->h_frames) (void)hipHostFree(c->h_frames);
     if (c->ev_frames) (void)hipEventDestroy(c->ev_frames);
@@ -1344,6 +1354,28 @@ int nr_render(nr_ctx *c, uint32_t *out, int W, int H, int max_steps, int loc, nr
     return nr_render_shard(c, out, W, H, H > 0 ? H : 1, 1, 0, max_steps, loc, stats);
 }
 
+// The QueryArgs of n rays but for the rays and the outputs: the view, scene and frame of the
+// context, the cursor and the statistics in d_qs (allocated by the caller).
+static QueryArgs query_args(const nr_ctx *c, long n, int W, int H, int max_steps) {
+    QueryArgs Q{};
+    Q.n = n; Q.W = W; Q.H = H;
+    Q.inv_w = 1.0 / (double)W;
+    Q.rcp_w = pow2_rcp(W); Q.rcp_h = pow2_rcp(H);
+    memcpy(Q.inv_view, c->inv_view, sizeof Q.inv_view);
+    Q.max_steps = max_steps; Q.scene = c->scene; Q.frame = c->frame;
+    Q.cursor = c->d_qs;
+    Q.stats = reinterpret_cast<unsigned long long *>(c->d_qs + 32);
+    return Q;
+}
+
+// The grid of a persistent launch over n rays or pixels (k_query, k_light_trace), by the CU count
+// as the frame tracer's: nr_set_occupancy's workgroups per CU, or 2 (one launch of rays is a single
+// frame's worth: the tail outweighs the bulk, default_bpc)
+static int query_grid(const nr_ctx *c, size_t n) {
+    const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : 2;
+    return (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)num_cus(c->device) * bpc));
+}
+
 // Ray queries: n caller-supplied rays (origins / dirs), or with origins == NULL the W x H pixel
 // rays of the context's view, through one k_query launch (nr_query.hip).  Always the fp32 MLP.
 static int query_rays(nr_ctx *c, const char *fn, const float *origins, const float *dirs, long n, int W, int H,
@@ -1357,14 +1389,7 @@ static int query_rays(nr_ctx *c, const char *fn, const float *origins, const flo
     HIPCHK(c, hipSetDevice(c->device));
     GET_STREAM(c, s);
     if (!c->d_qs) HIPCHK(c, hipMalloc(&c->d_qs, 128 + 4 * 8));
-    QueryArgs Q{};
-    Q.n = n; Q.W = W; Q.H = H;
-    Q.inv_w = 1.0 / (double)W;
-    Q.rcp_w = pow2_rcp(W); Q.rcp_h = pow2_rcp(H);
-    memcpy(Q.inv_view, c->inv_view, sizeof Q.inv_view);
-    Q.max_steps = max_steps; Q.scene = c->scene; Q.frame = c->frame;
-    Q.cursor = c->d_qs;
-    Q.stats = reinterpret_cast<unsigned long long *>(c->d_qs + 32);
+    QueryArgs Q = query_args(c, n, W, H, max_steps);
     Q.origins = origins; Q.dirs = dirs;
     Q.status = status; Q.steps = steps; Q.t = t; Q.position = position; Q.normal = normal;
     const size_t N = (size_t)n;
@@ -1387,13 +1412,9 @@ static int query_rays(nr_ctx *c, const char *fn, const float *origins, const flo
         if (position) { Q.position = q; q += 3 * N; }
         if (normal) { Q.normal = q; q += 3 * N; }
     }
-    // the grid by the CU count, as the frame tracer's: nr_set_occupancy's workgroups per CU, or 2
-    // (one launch of rays is a single frame's worth: the tail outweighs the bulk, default_bpc)
-    const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : 2;
-    const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + 255) / 256, (size_t)num_cus(c->device) * bpc));
     HIPCHK(c, hipEventRecord(c->ev0, s));
     HIPCHK(c, hipMemsetAsync(c->d_qs, 0, 128 + 4 * 8, s));
-    HIPCHK(c, launch_query(Q, c->mlp16, grid, s));
+    HIPCHK(c, launch_query(Q, c->mlp16, query_grid(c, N), s));
     HIPCHK(c, hipEventRecord(c->ev1, s));
     if (loc != NR_DEVICE) {
         if (status) HIPCHK(c, hipMemcpyAsync(status, Q.status, N * 4, hipMemcpyDeviceToHost, s));
@@ -1545,6 +1566,104 @@ int nr_render_aa(nr_ctx *c, uint32_t *out, int W, int H, int samples, int mode, 
         st.ms_total += ms_aa;
         *stats = st;
     }
+    return NR_OK;
+}
+
+// ---- ambient occlusion and soft shadows (nr_light.hip) ----
+
+// Three launches on the context's stream: the geometry buffer (k_query<true>) into context scratch,
+// k_light_trace over its pixels (ao and shadow), k_light_resolve where a frame is wanted.  No
+// host read in between: the tracer's cursor runs over all pixels, not over a list of the hits.
+int nr_render_lit(nr_ctx *c, uint32_t *out, int W, int H, int max_steps, const nr_light *light, float *ao, float *shadow,
+                  int loc, nr_stats *stats) {
+    if (!c || !light) return set_err(c, NR_E_INVALID, "nr_render_lit: NULL argument");
+    if (!out && !ao && !shadow) return set_err(c, NR_E_INVALID, "nr_render_lit: no output wanted");
+    int rc;
+    if ((rc = check_shape(c, W, H, H > 0 ? H : 1, 1, 0, max_steps)) != NR_OK) return rc;
+    if ((long)W * H > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_render_lit: bad size %dx%d", W, H);
+    if (max_steps < 1) return set_err(c, NR_E_INVALID, "nr_render_lit: max_steps < 1");
+    const nr_light &l = *light;
+    const float lf[8] = {l.dir[0], l.dir[1], l.dir[2], l.shadow_bias, l.shadow_k, l.ao_step, l.ao_strength, l.ambient};
+    for (float v : lf)
+        if (!std::isfinite(v)) return set_err(c, NR_E_INVALID, "nr_render_lit: a non-finite light field");
+    if (l.dir[0] == 0.0f && l.dir[1] == 0.0f && l.dir[2] == 0.0f) return set_err(c, NR_E_INVALID, "nr_render_lit: dir is zero");
+    if (l.shadow_steps < 0) return set_err(c, NR_E_INVALID, "nr_render_lit: shadow_steps < 0");
+    if (l.shadow_k < 0.0f || l.ao_step < 0.0f || l.ao_strength < 0.0f)
+        return set_err(c, NR_E_INVALID, "nr_render_lit: negative shadow_k, ao_step or ao_strength");
+    if (l.ambient < 0.0f || l.ambient > 1.0f) return set_err(c, NR_E_INVALID, "nr_render_lit: ambient outside 0..1");
+    if (c->dims.empty()) return set_err(c, NR_E_STATE, "nr_render_lit: no network loaded");
+    if (!c->fused)
+        return set_err(c, NR_E_FORMAT, "nr_render_lit: needs a [3|4, 32, ..., 32, 1] network (no layered fallback)");
+    if ((rc = check_scene(c)) != NR_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const size_t N = (size_t)W * H;
+    const bool host = loc != NR_DEVICE;
+    // ---- scratch: the geometry buffer, the values without a device buffer of the caller's, the frame's staging
+    if (!c->d_qs) HIPCHK(c, hipMalloc(&c->d_qs, 128 + 4 * 8));
+    if (!c->d_ls) HIPCHK(c, hipMalloc(&c->d_ls, 128 + 4 * 8));
+    if ((rc = ensure_buf(c, c->d_lgbuf, c->cap_lgbuf, 7 * N)) != NR_OK) return rc;
+    float *d_ao = host ? nullptr : ao, *d_shadow = host ? nullptr : shadow;
+    if ((rc = ensure_buf(c, c->d_lao, c->cap_lao, (d_ao ? 0 : N) + (d_shadow ? 0 : N))) != NR_OK) return rc;
+    if (!d_shadow) d_shadow = c->d_lao;
+    if (!d_ao) d_ao = d_shadow == c->d_lao ? c->d_lao + N : c->d_lao;
+    uint32_t *dout = out;
+    if (out && host) {
+        if ((rc = ensure_buf(c, c->d_out, c->cap_out, N)) != NR_OK) return rc;
+        dout = c->d_out;
+    }
+    // ---- pass A: the geometry buffer
+    QueryArgs Q = query_args(c, (long)N, W, H, max_steps);
+    Q.status = reinterpret_cast<int32_t *>(c->d_lgbuf);
+    Q.position = c->d_lgbuf + N;
+    Q.normal = c->d_lgbuf + 4 * N;
+    // ---- pass B: ao and shadow of every pixel
+    LightArgs X{};
+    X.n = (long)N; X.scene = c->scene; X.frame = c->frame;
+    X.status = Q.status; X.position = Q.position; X.normal = Q.normal;
+    for (int a = 0; a < 3; ++a) X.dir[a] = l.dir[a];
+    X.shadow_steps = l.shadow_steps; X.shadow_bias = l.shadow_bias; X.shadow_k = l.shadow_k;
+    X.ao_step = l.ao_step; X.ao_strength = l.ao_strength; X.ambient = l.ambient;
+    X.ao = d_ao; X.shadow = d_shadow;
+    X.cursor = c->d_ls;
+    X.stats = reinterpret_cast<unsigned long long *>(c->d_ls + 32);
+    const int grid = query_grid(c, N);
+    nr_stats st{};
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, hipMemsetAsync(c->d_qs, 0, 128 + 4 * 8, s));
+    HIPCHK(c, launch_query(Q, c->mlp16, grid, s));
+    HIPCHK(c, hipMemsetAsync(c->d_ls, 0, 128 + 4 * 8, s));
+    HIPCHK(c, launch_light_trace(X, c->mlp16, grid, s));
+    st.launches = 4;
+    if (out) {
+        // ---- pass C: the base colour times the light
+        RenderArgs A = render_args(c, W, H, H, H, 1, 0, max_steps);
+        A.out = dout;
+        A.frame = c->frame;
+        memcpy(A.inv_view, c->inv_view, sizeof A.inv_view);
+        memcpy(A.normal, c->normal, sizeof A.normal);
+        HIPCHK(c, launch_light_resolve(A, X, s));
+        st.launches += 1;
+    }
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (host) {
+        if (out) HIPCHK(c, hipMemcpyAsync(out, dout, N * 4, hipMemcpyDeviceToHost, s));
+        if (ao) HIPCHK(c, hipMemcpyAsync(ao, d_ao, N * 4, hipMemcpyDeviceToHost, s));
+        if (shadow) HIPCHK(c, hipMemcpyAsync(shadow, d_shadow, N * 4, hipMemcpyDeviceToHost, s));
+    }
+    unsigned long long hq[4], hl[2];
+    if (stats) {
+        HIPCHK(c, hipMemcpyAsync(hq, Q.stats, sizeof hq, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(hl, X.stats, sizeof hl, hipMemcpyDeviceToHost, s));
+    }
+    rc = end_timed(c, stats != nullptr, loc, s, &st.ms_total);
+    if (rc != NR_OK || !stats) return rc;
+    st.ray_steps = hq[0] + hl[0];
+    st.rays_hit = hq[1];
+    st.iterations = (int32_t)std::max(hq[2], hl[1]);
+    st.rays_shaded = hq[3];
+    st.shade_evals = (l.ao_strength > 0.0f ? 8ull : 4ull) * hq[3];
+    *stats = st;
     return NR_OK;
 }
 

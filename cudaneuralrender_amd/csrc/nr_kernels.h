@@ -187,6 +187,21 @@ struct AaArgs {
     unsigned long long *stats;    // [0] ray-steps, [1] rays that entered the sphere, [2] max iterations, [3] coloured
 };
 
+// Lighting (nr_light.hip; nr_render_lit): the W x H geometry buffer k_query<true> left in status /
+// position / normal, the light, and one ao and one shadow value per pixel.
+struct LightArgs {
+    long n;                       // W H <= 2^30
+    int scene, frame;
+    const int32_t *status;        // [n] NR_RAY_*
+    const float *position, *normal;  // [n][3], of the hits
+    float dir[3];                 // nr_light, field by field
+    int shadow_steps;
+    float shadow_bias, shadow_k, ao_step, ao_strength, ambient;
+    float *ao, *shadow;           // [n], both always written by k_light_trace
+    uint32_t *cursor;             // next pixel to deal (zeroed before the launch)
+    unsigned long long *stats;    // [0] shadow-ray steps, [1] the longest shadow ray's
+};
+
 // The lattice of nr_sample_grid / nr_mesh_grid / nr_extract_mesh: point (i, j, k) has linear index
 // (k ny + j) nx + i and coordinates origin[a] + (float)idx_a * step[a] (one f32 multiply, one add).
 struct LatticeArgs {
@@ -256,6 +271,8 @@ hipError_t launch_query(const QueryArgs &Q, const MlpArgs &M, int grid, hipStrea
 hipError_t launch_aa_detect(const AaArgs &X, hipStream_t st);
 hipError_t launch_aa_trace(const RenderArgs &A, const AaArgs &X, const MlpArgs &M, int grid, hipStream_t st);  // 4-wave workgroups
 hipError_t launch_aa_resolve(const AaArgs &X, hipStream_t st);
+hipError_t launch_light_trace(const LightArgs &X, const MlpArgs &M, int grid, hipStream_t st);  // 4-wave workgroups
+hipError_t launch_light_resolve(const RenderArgs &A, const LightArgs &X, hipStream_t st);  // A: W, H, out, view, colouring
 hipError_t launch_dense(const DenseArgs &D, int src, int grid, hipStream_t st);
 hipError_t launch_init_f(const RenderArgs &A, const FrameArgs *F, const QueueArgs &Q, long npix, long total,
                          int grid, hipStream_t st);

@@ -10,7 +10,8 @@ import ctypes
 import numpy as np
 
 from ._lib import (NR_AA_CONTRAST_DEFAULT, NR_AA_MODE, NR_COLOR_FACING, NR_COLOR_MATCAP, NR_DEVICE, NR_GROUP_ASYNC,
-                   NR_GROUP_COPY, NR_HOST, NR_PRECISION, NR_SCENE, NR_SCHEDULE, NRFrame, NRKernelProf, NRStats, check, lib)
+                   NR_GROUP_COPY, NR_HOST, NR_PRECISION, NR_SCENE, NR_SCHEDULE, NRFrame, NRKernelProf, NRLight, NRStats, check,
+                   lib)
 
 _FP = ctypes.POINTER(ctypes.c_float)
 
@@ -509,6 +510,49 @@ class Renderer:
         context's stream (set_stream).  Returns the stats dict when asked for, else the edge-pixel count."""
         st = self._render_aa(ctypes.c_void_p(out_ptr), W, H, samples, mode, contrast, max_steps, NR_DEVICE, with_stats)
         return st if with_stats else st["edge_pixels"]
+
+    # -- ambient occlusion and soft shadows
+    @staticmethod
+    def _light(light_dir, shadow_steps, shadow_bias, shadow_k, ao_step, ao_strength, ambient):
+        lt = NRLight()
+        lt.dir[:] = [float(v) for v in np.asarray(light_dir, np.float32).reshape(3)]
+        lt.shadow_steps = int(shadow_steps)
+        lt.shadow_bias, lt.shadow_k = float(shadow_bias), float(shadow_k)
+        lt.ao_step, lt.ao_strength, lt.ambient = float(ao_step), float(ao_strength), float(ambient)
+        return lt
+
+    def render_lit(self, W, H, light_dir, shadow_steps=64, shadow_bias=0.01, shadow_k=8.0, ao_step=0.02,
+                   ao_strength=2.0, ambient=0.3, max_steps=6000, buffers=False, with_stats=False):
+        """nr_render_lit: render()'s fp32 frame lit by one directional light (light_dir: from the
+        surface towards the light, used as given), every coloured pixel scaled by
+        ao * (ambient + (1 - ambient) * shadow * max(dot(n, light_dir), 0)): ao from four field samples
+        along the normal, shadow from a sphere-traced ray towards the light (soft for shadow_k > 0).
+        Always the fp32 MLP.  Returns the (H, W) uint32 image; buffers=True: (image, ao, shadow) with
+        the two (H, W) float32 factors; with_stats=True appends the stats dict."""
+        out = np.zeros((H, W), np.uint32)
+        ao = np.zeros((H, W), np.float32) if buffers else None
+        sh = np.zeros((H, W), np.float32) if buffers else None
+        lt = self._light(light_dir, shadow_steps, shadow_bias, shadow_k, ao_step, ao_strength, ambient)
+        st = NRStats()
+        self._chk(self._L.nr_render_lit(self._ctx, out.ctypes.data, int(W), int(H), int(max_steps), ctypes.byref(lt),
+                                        ao.ctypes.data if buffers else None, sh.ctypes.data if buffers else None,
+                                        NR_HOST, ctypes.byref(st) if with_stats else None))
+        res = (out, ao, sh) if buffers else (out,)
+        if with_stats:
+            res += (st.as_dict(),)
+        return res if len(res) > 1 else out
+
+    def render_lit_device(self, out_ptr, W, H, light_dir, shadow_steps=64, shadow_bias=0.01, shadow_k=8.0, ao_step=0.02,
+                          ao_strength=2.0, ambient=0.3, max_steps=6000, ao_ptr=None, shadow_ptr=None, with_stats=False):
+        """nr_render_lit into device buffers (e.g. torch tensors' data_ptr(): W * H uint32 for the
+        frame, W * H float32 for ao and shadow; None = that output is not wanted, but not all three),
+        on the context's stream (set_stream).  Without stats it returns without waiting."""
+        vp = [ctypes.c_void_p(p) if p else None for p in (out_ptr, ao_ptr, shadow_ptr)]
+        lt = self._light(light_dir, shadow_steps, shadow_bias, shadow_k, ao_step, ao_strength, ambient)
+        st = NRStats()
+        self._chk(self._L.nr_render_lit(self._ctx, vp[0], int(W), int(H), int(max_steps), ctypes.byref(lt), vp[1], vp[2],
+                                        NR_DEVICE, ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
 
     # -- volume sampling / isosurface extraction
     def sample_grid(self, origin, step, dims, with_stats=False):

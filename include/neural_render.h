@@ -253,6 +253,70 @@ int nr_render_gbuffer(nr_ctx *ctx, int W, int H, int max_steps, int32_t *status,
 int nr_render_aa(nr_ctx *ctx, uint32_t *out, int W, int H, int samples, int mode, int contrast,
                  int max_steps, int out_loc, long *edge_pixels, nr_stats *stats);
 
+/* ---- ambient occlusion and soft shadows ------------------------------------------ */
+/* (new symbols and one new struct only: NR_ABI_VERSION stays 3, nr_stats is unchanged) */
+typedef struct nr_light {
+    float dir[3];       /* from the surface towards the light, world space; used as given (not normalised) */
+    int   shadow_steps; /* at most this many march iterations per shadow ray; 0 = no shadows (shadow = 1) */
+    float shadow_bias;  /* shadow-ray origin = hit position + normal * shadow_bias */
+    float shadow_k;     /* penumbra sharpness; 0 = hard shadow */
+    float ao_step;      /* spacing of the 4 occlusion samples along the normal */
+    float ao_strength;  /* 0 = no ambient occlusion (ao = 1, no evaluations run) */
+    float ambient;      /* share of the light that no shadow removes, 0..1 */
+} nr_light;
+/* Renders the W x H frame of the context's view lit by one directional light: every coloured pixel
+ * of nr_render's frame is scaled by an ambient-occlusion factor and a soft-shadow factor taken from
+ * the same signed-distance field, in one call (a geometry buffer, one persistent lighting launch,
+ * one compositing launch; no host round trip).  All arithmetic is f32, one rounding per operation,
+ * no contraction; dot3(a, b) = (a0 b0 + a1 b1) + a2 b2; sat(x) = x for 0 < x <= 1, 1 above, else 0
+ * (NaN -> 0).  G is what nr_render_gbuffer(W, H, max_steps) returns for the context's view, scene
+ * and frame (status, position, normal); base is nr_render's W x H frame at NR_PRECISION_FP32 with
+ * the context's colouring and matcap; L = light->dir.
+ *  1. A pixel that is not NR_RAY_HIT has out = 0, ao = 1.0f, shadow = 1.0f.
+ *  2. Geometry of a HIT pixel.  p = G.position, n = G.normal, dd = dot3(n, L), ndl = dd > 0 ? dd : 0
+ *     (a NaN normal gives 0).
+ *  3. Ambient occlusion (ao_strength > 0).  For q = 0..3: h_q = (float)(q + 1) * ao_step, a_q = p +
+ *     n * h_q per component (multiply, then add), s_q = sceneSDF(a_q, mlp(a_q)) with the fp32 MLP (a
+ *     4-input network gets (float)frame), c_q = (h_q - s_q) * w_q with w = 1, 0.5, 0.25, 0.125.
+ *     occ = ((c_0 + c_1) + c_2) + c_3 and ao = sat(1.0f - ao_strength * occ).  With ao_strength == 0,
+ *     ao = 1.0f, nothing is evaluated and those shade_evals are not counted.
+ *  4. Shadow (shadow_steps > 0).  If ndl is 0, shadow = 0.0f and no ray is marched.  Otherwise the ray
+ *     o = p + n * shadow_bias (multiply, then add), d = L is marched exactly as nr_trace_rays marches
+ *     a ray -- the same entry, step and end conditions, shadow_steps in the place of max_steps, no
+ *     normals -- with one addition: res = 1.0f at the start, and at every iteration, once tstep =
+ *     sceneSDF(p, mlp(p)) is known and before tfar is tested, dist = tnear + travel and, if dist > 0,
+ *     r = shadow_k * tstep / dist (multiply, then an IEEE divide) and res = r where r < res.  (dist
+ *     is 0 at the first point of a ray that starts inside the bounding sphere, as every shadow ray
+ *     of a surface does: there the quotient would be +inf or NaN and says nothing; shadow_bias
+ *     decides how far that point is from the surface.)  The ray's status gives the value: MISS
+ *     1.0f; ESCAPED shadow_k > 0 ? sat(res) : 1.0f; HIT and LIMIT 0.0f.  With shadow_steps == 0,
+ *     shadow = 1.0f for every pixel and no ray is marched.
+ *  5. Composite.  f = ao * (ambient + (1.0f - ambient) * (shadow * ndl)); each of the r, g, b bytes c
+ *     of base(x, y) becomes (uint32)((float)c * f) by truncation, at most 255 (f exceeds 1 only for
+ *     a dir longer than 1); alpha stays base's.  With ao_strength = 0, shadow_steps = 0 and ambient
+ *     = 1, f is exactly 1 and out is nr_render's fp32 frame, bit for bit.
+ *  6. Settings and precision.  Always the fp32 MLP: nr_set_precision and nr_set_schedule are
+ *     ignored, as for the ray queries, and the call leaves the context's settings as it found
+ *     them.  The outputs depend only on the inputs: the same bits for any grid size, occupancy
+ *     (nr_set_occupancy) or order in which the pixels are dealt.
+ *  7. Outputs.  out (W H pixels), ao and shadow (W H floats each), index y * W + x: any may be NULL
+ *     but not all three; loc = NR_HOST or NR_DEVICE for all of them.  stats (may be NULL): ray_steps
+ *     = the geometry buffer's plus the sum of the shadow rays' steps; rays_hit and rays_shaded the
+ *     geometry buffer's; shade_evals = 4 per HIT, plus 4 per HIT with ambient occlusion on;
+ *     iterations = the larger of the primary and the shadow rays' longest; launches and ms_total
+ *     as elsewhere.
+ *  8. Errors.  NR_E_INVALID: ctx or light NULL, all three outputs NULL, W or H < 1, W H > 2^30,
+ *     max_steps < 1, shadow_steps < 0, a non-finite field, dir all zero, shadow_k, ao_step or
+ *     ao_strength negative, ambient outside 0..1.  NR_E_STATE: no network.  NR_E_FORMAT: a network
+ *     the fused kernels do not take, as for the queries (no layered fallback).  Everything else
+ *     nr_render would report for the same context is reported as nr_render reports it.
+ *  9. Scratch.  The context owns it and keeps it until nr_destroy: 28 bytes per pixel of geometry
+ *     buffer (status, position, normal), 8 bytes per pixel (ao, shadow) where the caller gave none
+ *     or gave host pointers (4 for one of the two), plus W H x 4 bytes of staging for a host out. */
+int nr_render_lit(nr_ctx *ctx, uint32_t *out /*W*H or NULL*/, int W, int H, int max_steps,
+                  const nr_light *light, float *ao /*W*H or NULL*/, float *shadow /*W*H or NULL*/,
+                  int loc, nr_stats *stats);
+
 /* ---- volume sampling / isosurface extraction ------------------------------------ */
 /* (new symbols only, as the ray queries: NR_ABI_VERSION stays 3)
  *

@@ -7,7 +7,9 @@
 // --precision {fp32,bf16,fp16,fp32x3}, --scene {v1,tanh}, --ppm (also write a .ppm),
 // --camera {eigen,f64}, --gpus N (each frame's row-band shards on N GPUs, one RCCL gather:
 // nr_group_render_batch), --aa S / --aa-full / --aa-contrast N (the single-GPU frame antialiased
-// from S x S samples per edge pixel, or per pixel: nr_render_aa).
+// from S x S samples per edge pixel, or per pixel: nr_render_aa), --light x,y,z with --shadow-steps,
+// --shadow-k, --shadow-bias, --ao, --ao-step, --ambient (the single-GPU frame with ambient
+// occlusion and soft shadows from one directional light: nr_render_lit).
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -45,6 +47,10 @@ static int numGpus = 0;
 // --aa S: the frame through nr_render_aa with S x S samples (0 = nr_render, as without the flag);
 // --aa-full: every pixel instead of the edge pixels; --aa-contrast N: the edge rule's threshold
 static int aaSamples = 0, aaMode = NR_AA_ADAPTIVE, aaContrast = NR_AA_CONTRAST_DEFAULT;
+// --light x,y,z: the frame through nr_render_lit, lit from that direction (surface towards the
+// light, used as given); the other fields of nr_light by their flags, render_lit's defaults else
+static bool useLight = false;
+static nr_light light = {{0.0f, 0.0f, 0.0f}, 64, 0.01f, 8.0f, 0.02f, 2.0f, 0.3f};
 static std::vector<nr_ctx *> groupCtx;
 static nr_group *group = nullptr;
 
@@ -73,7 +79,11 @@ static void usage() {
                  "\t--camera f64|eigen (default f64: exact matrices rounded once; eigen: a restatement of Eigen's scalar float path, unpinned)\n"
                  "\t--gpus N split every frame into row-band shards over N GPUs (one RCCL gather per frame)\n"
                  "\t--aa S antialias edge pixels from S x S samples (1..8; single GPU, always fp32)  --aa-full every pixel\n"
-                 "\t--aa-contrast N edge threshold 0..255 (default 32)\n";
+                 "\t--aa-contrast N edge threshold 0..255 (default 32)\n"
+                 "\t--light x,y,z ambient occlusion and soft shadows from one directional light (surface towards the light;\n"
+                 "\t\tsingle GPU, always fp32)  --shadow-steps N (default 64; 0: no shadows)  --shadow-k K penumbra\n"
+                 "\t\tsharpness (default 8; 0: hard)  --shadow-bias B (default 0.01)  --ao STRENGTH (default 2; 0: off)\n"
+                 "\t\t--ao-step H sample spacing (default 0.02)  --ambient A unshadowed share 0..1 (default 0.3)\n";
 }
 
 static void parseCmdOptions(int argc, char **argv) {
@@ -97,6 +107,16 @@ static void parseCmdOptions(int argc, char **argv) {
     if (getCmdOption(b, e, "--aa")) aaSamples = atoi(getCmdOption(b, e, "--aa"));
     if (cmdOptionExists(b, e, "--aa-full")) aaMode = NR_AA_FULL;
     if (getCmdOption(b, e, "--aa-contrast")) aaContrast = atoi(getCmdOption(b, e, "--aa-contrast"));
+    if (getCmdOption(b, e, "--light")) {
+        useLight = sscanf(getCmdOption(b, e, "--light"), "%f,%f,%f", &light.dir[0], &light.dir[1], &light.dir[2]) == 3;
+        if (!useLight) { std::cerr << "--light takes x,y,z\n"; exit(2); }
+    }
+    if (getCmdOption(b, e, "--shadow-steps")) light.shadow_steps = atoi(getCmdOption(b, e, "--shadow-steps"));
+    if (getCmdOption(b, e, "--shadow-k")) light.shadow_k = (float)atof(getCmdOption(b, e, "--shadow-k"));
+    if (getCmdOption(b, e, "--shadow-bias")) light.shadow_bias = (float)atof(getCmdOption(b, e, "--shadow-bias"));
+    if (getCmdOption(b, e, "--ao")) light.ao_strength = (float)atof(getCmdOption(b, e, "--ao"));
+    if (getCmdOption(b, e, "--ao-step")) light.ao_step = (float)atof(getCmdOption(b, e, "--ao-step"));
+    if (getCmdOption(b, e, "--ambient")) light.ambient = (float)atof(getCmdOption(b, e, "--ambient"));
     if (getCmdOption(b, e, "--max-steps")) NR_MAX_STEPS = atoi(getCmdOption(b, e, "--max-steps"));
     if (getCmdOption(b, e, "--scene")) NR_SCENE_MODE = std::string(getCmdOption(b, e, "--scene")) == "tanh" ? NR_SCENE_TANH : NR_SCENE_V1;
     if (getCmdOption(b, e, "--precision")) {
@@ -154,6 +174,24 @@ static bool renderAA(unsigned *d_output, const float *invView, const float *norm
     return true;
 }
 
+// The frame through nr_render_lit on the network's context, with the settings render_kernel applies.
+static bool renderLit(unsigned *d_output, const float *invView, const float *normal) {
+    nr_ctx *c = nn.context();
+    nr_stats st{};
+    if (!c || nr_set_view(c, invView, normal, frameNumber) != NR_OK || nr_set_static(c, colorType, numInputs) != NR_OK ||
+        nr_set_scene(c, NR_SCENE_MODE) != NR_OK ||
+        (colorType == NR_COLOR_MATCAP &&
+         nr_set_matcap(c, matcap.hostData.get(), (int)matcap.shape.x, (int)matcap.shape.y) != NR_OK) ||
+        nr_render_lit(c, d_output, (int)width, (int)height, NR_MAX_STEPS, &light, nullptr, nullptr, NR_DEVICE, &st) != NR_OK) {
+        printf("nr_render_lit: %s\n", nr_last_error(c));
+        return false;
+    }
+    if (saveCount == 0)
+        printf("lighting: %llu hit pixels, %llu ray-steps with the shadow rays\n", (unsigned long long)st.rays_shaded,
+               (unsigned long long)st.ray_steps);
+    return true;
+}
+
 static bool generateSingleImage() {
     if (numGpus > 0) {  // the frame across numGpus GPUs
         if (!group && !groupInit()) return false;
@@ -184,7 +222,9 @@ static bool generateSingleImage() {
     (void)hipDeviceSynchronize();
     auto t0 = std::chrono::steady_clock::now();
     dim3_ block{8, 8, 1}, grid{(width + 7) / 8, (height + 7) / 8, 1};
-    if (aaSamples > 0) {
+    if (useLight) {
+        if (!renderLit(d_output, invView, normal)) return false;
+    } else if (aaSamples > 0) {
         if (!renderAA(d_output, invView, normal)) return false;
     } else {
         render_kernel(grid, block, d_output, width, height, (unsigned)numInputs, nn, matcap);
