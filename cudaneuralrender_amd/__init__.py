@@ -9,6 +9,7 @@ import os
 from ._lib import (LIB_PATH, NR_ENDGAME_DEFAULT, NR_PRECISION, NR_RAY_ESCAPED, NR_RAY_HIT, NR_RAY_LIMIT,  # noqa: F401
                    NR_RAY_MISS, NR_SCENE, NR_SCHEDULE, NRError, lib)
 from ._lib import NR_AA_CONTRAST_DEFAULT, NR_AA_MODE, NRLight  # noqa: F401
+from ._lib import NR_PROJ_CONVERGED, NR_PROJ_FLAT, NR_PROJ_LIMIT, NRProjectOpts  # noqa: F401
 from .renderer import (NR_COLOR_FACING, NR_COLOR_MATCAP, Group, Renderer, assemble_shards, camera,  # noqa: F401
                        load_png, pack_fp32_pruned, pack_x3, read_keras_h5, save_obj, save_png, save_ppm, shard_rows, batch_frames_per_launch,
                        group_layout)

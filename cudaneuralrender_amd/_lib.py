@@ -24,6 +24,8 @@ NR_RAY_MISS, NR_RAY_ESCAPED, NR_RAY_HIT, NR_RAY_LIMIT = 0, 1, 2, 3
 # nr_render_aa: which pixels are resolved from their S x S samples, and the default edge contrast
 NR_AA_MODE = {"adaptive": 0, "full": 1}
 NR_AA_CONTRAST_DEFAULT = 32
+# status of a projected point (nr_project_points)
+NR_PROJ_CONVERGED, NR_PROJ_LIMIT, NR_PROJ_FLAT = 0, 1, 2
 
 # every symbol include/neural_render.h declares
 EXPORTS = [
@@ -40,7 +42,7 @@ EXPORTS = [
     "nr_set_endgame", "nr_group_create_ex", "nr_group_synchronize", "nr_group_layout",
     "nr_trace_rays", "nr_render_gbuffer", "nr_render_aa", "nr_render_lit",
     "nr_sample_grid", "nr_mesh_grid", "nr_extract_mesh", "nr_obj_save",
-    "nr_mlp_gradient",
+    "nr_mlp_gradient", "nr_project_points",
     "nr_pack_fp32_pruned", "nr_set_prune", "nr_prune_info", "nr_prune_redos",
 ]
 
@@ -82,6 +84,16 @@ class NRLight(ctypes.Structure):
         ("ao_step", ctypes.c_float),
         ("ao_strength", ctypes.c_float),
         ("ambient", ctypes.c_float),
+    ]
+
+
+class NRProjectOpts(ctypes.Structure):
+    """nr_project_opts: the level set, tolerance and step limits of nr_project_points."""
+    _fields_ = [
+        ("iso", ctypes.c_float),
+        ("tol", ctypes.c_float),
+        ("max_step", ctypes.c_float),
+        ("max_iters", ctypes.c_int),
     ]
 
 
@@ -161,6 +173,8 @@ def lib():
         "nr_assemble_shards": (I, [P, P, ctypes.c_size_t, P, I, I, I, I, I]),
         "nr_mlp_forward": (I, [P, P, P, L64, I]),
         "nr_mlp_gradient": (I, [P, P, L64, P, P, P, I, ctypes.POINTER(NRStats)]),
+        "nr_project_points": (I, [P, P, L64, ctypes.POINTER(NRProjectOpts), P, P, P, P, P, P, I,
+                                  ctypes.POINTER(NRStats)]),
         "nr_layer_forward": (I, [P, I, P, P, L64, I]),
         "nr_camera": (I, [F, F, F, F, F, FP, FP]),
         "nr_camera_ex": (I, [F, F, F, F, F, I, FP, FP]),

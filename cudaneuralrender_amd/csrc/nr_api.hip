@@ -106,6 +106,8 @@ struct nr_ctx {
     size_t cap_lgbuf = 0;
     float *d_lao = nullptr;
     size_t cap_lao = 0;
+    // projection (nr_project_points): the point cursor on its own 128-byte line + 4 x u64 counters
+    uint32_t *d_ps = nullptr;
     // volume sampling and isosurface extraction (nr_sample_grid, nr_mesh_grid, nr_extract_mesh):
     // the lattice of nr_extract_mesh (4 B per point; the staging of host lattices too), the
     // extraction's scratch (MeshArgs: 4 B per point + 24 B per 256 points) and the staging of
@@ -1152,6 +1154,7 @@ int nr_destroy(nr_ctx *c) {
     dfree(c->d_qs); dfree(c->d_qio);
     dfree(c->d_aas); dfree(c->d_aalist); dfree(c->d_aaacc);
     dfree(c->d_ls); dfree(c->d_lgbuf); dfree(c->d_lao);
+    dfree(c->d_ps);
     dfree(c->d_grid); dfree(c->d_mesh); dfree(c->d_mio);
     if (c->h_frames) (void)hipHostFree(c->h_frames);
     if (c->ev_frames) (void)hipEventDestroy(c->ev_frames);
@@ -2067,6 +2070,92 @@ int nr_mlp_gradient(nr_ctx *c, const float *X, long n, float *value, float *grad
     const int rc = end_timed(c, stats != nullptr, loc, s, &st.ms_total);
     if (rc == NR_OK && stats) *stats = st;
     return rc;
+}
+
+// Projection onto a level set: one persistent k_project launch (nr_project.hip).  Always the fp32 MLP.
+#ifndef NR_PROJ_COMPACT
+#define NR_PROJ_COMPACT 1  // pack a draining wave's live points into its lowest tiles (0: A/B builds)
+#endif
+int nr_project_points(nr_ctx *c, const float *X, long n, const nr_project_opts *opts, float *position, float *value,
+                      float *normal, float *distance, int32_t *iters, int32_t *status, int loc, nr_stats *stats) {
+    if (!c) return set_err(nullptr, NR_E_INVALID, "nr_project_points: ctx is NULL");
+    if (!opts) return set_err(c, NR_E_INVALID, "nr_project_points: opts is NULL");
+    if (n < 0 || n > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_project_points: n = %ld outside [0, 2^30]", n);
+    if (n > 0 && !X) return set_err(c, NR_E_INVALID, "nr_project_points: X is NULL");
+    if (!position && !value && !normal && !distance && !iters && !status)
+        return set_err(c, NR_E_INVALID, "nr_project_points: every output is NULL");
+    if (!std::isfinite(opts->iso) || !std::isfinite(opts->tol) || !std::isfinite(opts->max_step))
+        return set_err(c, NR_E_INVALID, "nr_project_points: iso, tol and max_step must be finite");
+    if (opts->tol < 0.0f || opts->max_step < 0.0f)
+        return set_err(c, NR_E_INVALID, "nr_project_points: tol = %g or max_step = %g is negative", opts->tol, opts->max_step);
+    if (opts->max_iters < 0 || opts->max_iters > 4096)
+        return set_err(c, NR_E_INVALID, "nr_project_points: max_iters = %d outside 0..4096", opts->max_iters);
+    if (c->dims.empty()) return set_err(c, NR_E_STATE, "nr_project_points: no network loaded");
+    if (!c->fused)
+        return set_err(c, NR_E_FORMAT, "nr_project_points: needs a [3|4, 32, ..., 32, 1] network (no layered fallback)");
+    if (!c->d_gpack16)
+        return set_err(c, NR_E_FORMAT, "nr_project_points: more than %d hidden 32 x 32 layers", GRAD_MAX_HIDDEN);
+    nr_stats st{};
+    if (n == 0) { if (stats) *stats = st; return NR_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    constexpr size_t PS_BYTES = 128 + 4 * 8;
+    if (!c->d_ps) HIPCHK(c, hipMalloc(&c->d_ps, PS_BYTES));
+    const size_t N = (size_t)n, in0 = (size_t)c->dims[0];
+    ProjArgs A{};
+    A.X = X; A.n = n;
+    A.iso = opts->iso; A.tol = opts->tol; A.max_step = opts->max_step; A.max_iters = opts->max_iters;
+    A.position = position; A.value = value; A.normal = normal; A.distance = distance;
+    A.iters = iters; A.status = status;
+    A.gb = c->d_gpack16; A.gb_bytes = c->gpack_bytes;
+    A.compact = NR_PROJ_COMPACT;
+    A.cursor = c->d_ps;
+    A.stats = reinterpret_cast<unsigned long long *>(c->d_ps + 32);
+    if (loc != NR_DEVICE) {
+        // staging, in 4-byte words: the points, then every output the caller asked for
+        const size_t need = N * in0 + (position ? 3 * N : 0) + (value ? N : 0) + (normal ? 3 * N : 0) +
+                            (distance ? N : 0) + (iters ? N : 0) + (status ? N : 0);
+        int rc;
+        if ((rc = ensure_buf(c, c->d_io, c->cap_io, need)) != NR_OK) return rc;
+        float *q = c->d_io;
+        HIPCHK(c, hipMemcpyAsync(q, X, N * in0 * 4, hipMemcpyHostToDevice, s));
+        A.X = q; q += N * in0;
+        if (position) { A.position = q; q += 3 * N; }
+        if (value) { A.value = q; q += N; }
+        if (normal) { A.normal = q; q += 3 * N; }
+        if (distance) { A.distance = q; q += N; }
+        if (iters) { A.iters = reinterpret_cast<int32_t *>(q); q += N; }
+        if (status) { A.status = reinterpret_cast<int32_t *>(q); q += N; }
+    }
+    const MlpArgs M = c->mlp16;
+    if (project_lds_bytes(M, A) > 64 * 1024)
+        return set_err(c, NR_E_FORMAT, "nr_project_points: the packs exceed 64 KB of LDS");
+    // two workgroups per CU are resident (their LDS: the two packs), and the launch is persistent:
+    // nr_set_occupancy's workgroups per CU, or the resident two
+    const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : 2;
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + 255) / 256, (size_t)num_cus(c->device) * bpc));
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, hipMemsetAsync(c->d_ps, 0, PS_BYTES, s));
+    HIPCHK(c, launch_project(A, M, grid, s));
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (loc != NR_DEVICE) {
+        if (position) HIPCHK(c, hipMemcpyAsync(position, A.position, 3 * N * 4, hipMemcpyDeviceToHost, s));
+        if (value) HIPCHK(c, hipMemcpyAsync(value, A.value, N * 4, hipMemcpyDeviceToHost, s));
+        if (normal) HIPCHK(c, hipMemcpyAsync(normal, A.normal, 3 * N * 4, hipMemcpyDeviceToHost, s));
+        if (distance) HIPCHK(c, hipMemcpyAsync(distance, A.distance, N * 4, hipMemcpyDeviceToHost, s));
+        if (iters) HIPCHK(c, hipMemcpyAsync(iters, A.iters, N * 4, hipMemcpyDeviceToHost, s));
+        if (status) HIPCHK(c, hipMemcpyAsync(status, A.status, N * 4, hipMemcpyDeviceToHost, s));
+    }
+    unsigned long long hs[3];
+    if (stats) HIPCHK(c, hipMemcpyAsync(hs, A.stats, sizeof hs, hipMemcpyDeviceToHost, s));
+    const int rc = end_timed(c, stats != nullptr, loc, s, &st.ms_total);
+    if (rc != NR_OK || !stats) return rc;
+    st.ray_steps = hs[0];
+    st.rays_shaded = hs[1];
+    st.iterations = (int32_t)hs[2];
+    st.launches = 2;  // the counters' memset and k_project
+    *stats = st;
+    return NR_OK;
 }
 
 int nr_layer_forward(nr_ctx *c, int layer, const float *A, float *Z, long n, int loc) {

@@ -44,7 +44,7 @@ constexpr int MAX_HIDDEN = 16;
 NR_HD constexpr inline int pk_final(int nh) { return PK_HID + nh * PK_HID_STRIDE; }
 NR_HD constexpr inline int pk_floats(int nh) { return pk_final(nh) + 36; }
 
-// Backward (gradient) pack beside the fp32 one (pack_grad_16; nr_grad.hip), in floats, raw
+// Backward (gradient) pack beside the fp32 one (pack_grad_16; nr_grad.h), in floats, raw
 // (unscaled) weights.  The backward pass of hidden layer j is the forward's MFMA loop on the
 // transposed kernel: row (A operand) = the layer's input unit, k = its output unit, so every
 // chain runs over the output units 0..31 ascending.  The gradient of register k of lane group g

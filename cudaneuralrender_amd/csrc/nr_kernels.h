@@ -260,9 +260,27 @@ struct GradArgs {
     int gb_bytes;
 };
 
+// Projection onto a level set (nr_project.hip k_project; nr_project_points): every point writes its
+// slot of the outputs that are not NULL.
+struct ProjArgs {
+    const float *X;               // [n][in0]
+    long n;                       // <= 2^30
+    float iso, tol, max_step;     // nr_project_opts, field by field
+    int max_iters;
+    float *position, *value, *normal, *distance;  // [n][3], [n], [n][3], [n]
+    int32_t *iters, *status;      // [n]: steps taken, NR_PROJ_*
+    const float *gb;              // the backward pack, staged after the fp32 pack (as GradArgs)
+    int gb_bytes;
+    int compact;                  // pack the live slots into the lowest tiles once the cursor is past n
+    uint32_t *cursor;             // next point to deal (zeroed before the launch)
+    unsigned long long *stats;    // [0] evaluations, [1] converged points, [2] the largest evaluation count
+};
+
 int dense_lds_bytes(int in, int out);
 int grad_lds_bytes(const MlpArgs &M, const GradArgs &G);  // one k_grad workgroup's dynamic LDS
 hipError_t launch_grad(const GradArgs &G, const MlpArgs &M, int grid, hipStream_t st);  // 4-wave workgroups
+int project_lds_bytes(const MlpArgs &M, const ProjArgs &P);  // one k_project workgroup's dynamic LDS
+hipError_t launch_project(const ProjArgs &P, const MlpArgs &M, int grid, hipStream_t st);  // 4-wave workgroups
 hipError_t launch_grid(const GridArgs &G, const MlpArgs &M, int grid, hipStream_t st);
 hipError_t launch_vnormal(const VNormalArgs &V, const MlpArgs &M, int grid, hipStream_t st);
 hipError_t launch_mesh_count(const MeshArgs &A, hipStream_t st);  // k_mesh_count, then k_mesh_scan

@@ -117,7 +117,7 @@ __device__ __forceinline__ void f32_hidden7_stream(const float *s, float (&a)[NT
 // the chains of the next layer map to the same values).  Every VALU instruction costs f32
 // matrix time on gfx950 (profiles/r1_mfma_peak.txt), and this halves the activation VALU.
 // NH == 7 (the caller checks nh == 7): the stream below for NT <= 2 with the clamped ReLU
-// MK (nr_grad.hip; nh <= GRAD_MAX_HIDDEN): mk[t] receives tile t's ReLU masks, z > 0 of ReLU
+// MK (nr_grad.h; nh <= GRAD_MAX_HIDDEN): mk[t] receives tile t's ReLU masks, z > 0 of ReLU
 // layer l's register k in bit 8 (l & 3) + k of word l >> 2 (mk zeroed by the caller).  Both ReLU
 // forms give +0 exactly where z <= 0 (z is never -0: its chain starts from +0) and a positive
 // value elsewhere, so the bit is min(bits of the activation, 1): v_min_u32 + v_lshl_or_b32.

@@ -10,8 +10,8 @@ import ctypes
 import numpy as np
 
 from ._lib import (NR_AA_CONTRAST_DEFAULT, NR_AA_MODE, NR_COLOR_FACING, NR_COLOR_MATCAP, NR_DEVICE, NR_GROUP_ASYNC,
-                   NR_GROUP_COPY, NR_HOST, NR_PRECISION, NR_SCENE, NR_SCHEDULE, NRFrame, NRKernelProf, NRLight, NRStats, check,
-                   lib)
+                   NR_GROUP_COPY, NR_HOST, NR_PRECISION, NR_SCENE, NR_SCHEDULE, NRFrame, NRKernelProf, NRLight, NRProjectOpts,
+                   NRStats, check, lib)
 
 _FP = ctypes.POINTER(ctypes.c_float)
 
@@ -665,6 +665,46 @@ class Renderer:
         st = NRStats()
         self._chk(self._L.nr_mlp_gradient(self._ctx, vp[0], int(n), *vp[1:], NR_DEVICE,
                                           ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
+    PROJECT_OUTPUTS = ("position", "value", "normal", "distance", "iters", "status")
+
+    def project_points(self, X, iso=0.0, tol=1e-5, max_step=0.25, max_iters=32, outputs=PROJECT_OUTPUTS, with_stats=False):
+        """nr_project_points on a host array X [n, dims[0]]: every point moved onto the level set
+        {network value == iso} by Newton steps along the analytic gradient, in one launch.  Returns a
+        dict of the numpy arrays named in outputs (at least one of "position" [n, 3], "value" [n],
+        "normal" [n, 3], "distance" [n], "iters" [n] int32, "status" [n] int32 = NR_PROJ_*).  max_step:
+        the longest step in world units, 0 = unlimited.  Always the fp32 MLP."""
+        X = np.ascontiguousarray(X, np.float32)
+        if X.ndim != 2:
+            raise ValueError(f"X must be [n, inputs], got {X.shape}")
+        unknown = [k for k in outputs if k not in self.PROJECT_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}")
+        n = X.shape[0]
+        shape = {"position": ((n, 3), np.float32), "value": ((n,), np.float32), "normal": ((n, 3), np.float32),
+                 "distance": ((n,), np.float32), "iters": ((n,), np.int32), "status": ((n,), np.int32)}
+        out = {k: np.zeros(*shape[k]) for k in self.PROJECT_OUTPUTS if k in outputs}
+        ptr = [out[k].ctypes.data if k in out else None for k in self.PROJECT_OUTPUTS]
+        opts = NRProjectOpts(float(iso), float(tol), float(max_step), int(max_iters))
+        st = NRStats()
+        self._chk(self._L.nr_project_points(self._ctx, X.ctypes.data, n, ctypes.byref(opts), *ptr, NR_HOST,
+                                            ctypes.byref(st) if with_stats else None))
+        return (out, st.as_dict()) if with_stats else out
+
+    def project_points_device(self, x_ptr, n, iso=0.0, tol=1e-5, max_step=0.25, max_iters=32, position_ptr=None,
+                              value_ptr=None, normal_ptr=None, distance_ptr=None, iters_ptr=None, status_ptr=None,
+                              with_stats=False):
+        """nr_project_points on device buffers (e.g. torch tensors' data_ptr(): float32 X [n, dims[0]],
+        position [n, 3], value [n], normal [n, 3], distance [n], int32 iters [n], status [n]); None =
+        that output is not wanted.  Runs on the context's stream (set_stream) and, without stats,
+        returns without waiting."""
+        vp = [ctypes.c_void_p(p) if p else None
+              for p in (x_ptr, position_ptr, value_ptr, normal_ptr, distance_ptr, iters_ptr, status_ptr)]
+        opts = NRProjectOpts(float(iso), float(tol), float(max_step), int(max_iters))
+        st = NRStats()
+        self._chk(self._L.nr_project_points(self._ctx, vp[0], int(n), ctypes.byref(opts), *vp[1:], NR_DEVICE,
+                                            ctypes.byref(st) if with_stats else None))
         return st.as_dict() if with_stats else None
 
     def layer_forward(self, layer, A):

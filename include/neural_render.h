@@ -486,6 +486,61 @@ int nr_mlp_forward(nr_ctx *ctx, const float *X, float *Y, long n, int loc);
  * hidden 32 x 32 layers: there is no layered fallback).  n = 0 returns NR_OK without a launch. */
 int nr_mlp_gradient(nr_ctx *ctx, const float *X /*[n][dims[0]]*/, long n, float *value /*[n] or NULL*/,
                     float *grad /*[n][dims[0]] or NULL*/, float *normal /*[n][3] or NULL*/, int loc, nr_stats *stats);
+
+/* Projection of points onto a level set of the network (new symbols only: NR_ABI_VERSION stays 3):
+ * per point of X, Newton steps along the analytic gradient until the network's value is within tol
+ * of iso, all in one persistent launch.  Networks as for nr_mlp_gradient.
+ *  All arithmetic is f32, one rounding per operation, no contraction;
+ *  dot3(a, b) = (a0 b0 + a1 b1) + a2 b2.  Per point: p = the first three columns of X, p0 = p; a
+ *  4-input network takes its 4th input w from X and holds it constant (as nr_mlp_gradient: it is not
+ *  the context's frame).  For it = 0, 1, ...:
+ *    1. (v, g) = the bits nr_mlp_gradient gives for value and grad at (p[, w]).
+ *    2. r = v - iso; at it == 0, r0 = r.
+ *    3. If |r| <= tol: NR_PROJ_CONVERGED, stop.
+ *    4. Otherwise, if it == max_iters: NR_PROJ_LIMIT, stop.
+ *    5. gg = dot3(g, g) over the first three components.  If !(gg > 0): NR_PROJ_FLAT, stop.
+ *    6. t = r / gg (the IEEE divide).
+ *    7. If max_step > 0: m = |r| / sqrtf(gg), and where m > max_step, t = t * (max_step / m).
+ *    8. p_c = p_c - g_c * t for c = 0..2 (multiply, then subtract); the next iteration follows.
+ *  Outputs, all at the final p: position = p; value = v (the bits of nr_mlp_forward at position);
+ *  normal = the device normalize3(g) (the bits of nr_mlp_gradient's normal at position; NaN for a
+ *  zero gradient); iters = it, the steps taken; status = NR_PROJ_*; distance = sqrtf(dot3(d, d)) with
+ *  d_c = p_c - p0_c, negated where r0 < 0 (-0.0 where such a point took no step).
+ *  - max_iters = 0 is nr_mlp_gradient plus a status.
+ *  - A point's outputs depend only on that point and on opts: the same bits for any n, order, split
+ *    into calls, grid size or occupancy.  Non-finite inputs: unspecified outputs, no fault, and at
+ *    most max_iters + 1 evaluations.
+ *  - nr_set_precision and nr_set_schedule are ignored, as for the ray queries; the call leaves the
+ *    context's settings as it found them.
+ *  - position [n][3], value [n], normal [n][3], distance [n], iters [n], status [n]: any may be NULL,
+ *    not all six.  loc = NR_HOST or NR_DEVICE for all the pointers.
+ *  - stats (may be NULL): ray_steps = the evaluations (iters + 1 per point, summed), rays_shaded =
+ *    the CONVERGED points, iterations = the largest evaluation count of a point, launches, ms_total;
+ *    everything else 0.
+ *  What it is not: a Newton step along the gradient lands on the level set, in general not on its
+ *  point nearest to p0, and the network is only approximately a distance field.  distance is the
+ *  length of the chord from p0 to position, not a proven distance to the surface.
+ *  iso = 0 is the surface nr_render shows for NR_SCENE_TANH (the network's zero set);
+ *  NR_SCENE_ROUND's is iso = atanhf(0.04).
+ * Errors: NR_E_INVALID (ctx or opts NULL, n < 0, n > 2^30, X NULL with n > 0, every output NULL, tol
+ * or max_step negative, a field of opts not finite, max_iters outside 0..4096), NR_E_STATE (no
+ * network), NR_E_FORMAT (what nr_mlp_gradient refuses: a network the fused kernels do not take, or
+ * more than 7 hidden 32 x 32 layers).  n = 0 returns NR_OK without a launch and leaves the outputs
+ * untouched. */
+#define NR_PROJ_CONVERGED 0  /* |value - iso| <= tol at the returned position */
+#define NR_PROJ_LIMIT     1  /* max_iters steps taken and still not within tol */
+#define NR_PROJ_FLAT      2  /* gradient zero or not a number: no step can be taken */
+typedef struct nr_project_opts {
+    float iso;       /* project onto {network value == iso} */
+    float tol;       /* >= 0 */
+    float max_step;  /* longest step, in world units; 0 = unlimited */
+    int   max_iters; /* 0..4096 steps per point */
+} nr_project_opts;
+int nr_project_points(nr_ctx *ctx, const float *X /*[n][dims[0]]*/, long n, const nr_project_opts *opts,
+                      float *position /*[n][3]*/, float *value /*[n]*/, float *normal /*[n][3]*/,
+                      float *distance /*[n]*/, int32_t *iters /*[n]*/, int32_t *status /*[n]*/,
+                      int loc, nr_stats *stats);
+
 /* One DenseLayer::forward (denseLayer.cu:229-278) on device buffers: layer l of the
  * loaded network applied to A [n][dims[l]] -> Z [n][dims[l+1]]. */
 int nr_layer_forward(nr_ctx *ctx, int layer, const float *A, float *Z, long n, int loc);
