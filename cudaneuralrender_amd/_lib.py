@@ -41,7 +41,7 @@ EXPORTS = [
     "nr_group_create", "nr_group_destroy", "nr_group_size", "nr_group_render_batch", "nr_pack_x3",
     "nr_set_endgame", "nr_group_create_ex", "nr_group_synchronize", "nr_group_layout",
     "nr_trace_rays", "nr_render_gbuffer", "nr_render_aa", "nr_render_lit",
-    "nr_sample_grid", "nr_mesh_grid", "nr_extract_mesh", "nr_obj_save",
+    "nr_sample_grid", "nr_mesh_grid", "nr_extract_mesh", "nr_extract_mesh_sparse", "nr_obj_save",
     "nr_mlp_gradient", "nr_project_points",
     "nr_pack_fp32_pruned", "nr_set_prune", "nr_prune_info", "nr_prune_redos",
 ]
@@ -158,6 +158,8 @@ def lib():
         "nr_mesh_grid": (I, [P, P, FP, FP, IP, F, P, L64, P, L64, ctypes.POINTER(L64), ctypes.POINTER(L64), I]),
         "nr_extract_mesh": (I, [P, FP, FP, IP, F, P, P, L64, P, L64, ctypes.POINTER(L64), ctypes.POINTER(L64), I,
                                 ctypes.POINTER(NRStats)]),
+        "nr_extract_mesh_sparse": (I, [P, FP, FP, IP, F, I, F, P, P, P, L64, P, L64, ctypes.POINTER(L64), ctypes.POINTER(L64),
+                                       ctypes.POINTER(L64), I, ctypes.POINTER(NRStats)]),
         "nr_obj_save": (I, [ctypes.c_char_p, P, L64, P, P, L64]),
         "nr_render_shard": (I, [P, P, I, I, I, I, I, I, I, ctypes.POINTER(NRStats)]),
         "nr_render_batch": (I, [P, ctypes.POINTER(NRFrame), I, I, I, I, I, I, I, I, ctypes.POINTER(NRStats)]),

@@ -118,6 +118,11 @@ struct nr_ctx {
     size_t cap_mesh = 0;
     float *d_mio = nullptr;
     size_t cap_mio = 0;
+    // brick-sparse extraction (nr_extract_mesh_sparse; SparseArgs): the per-brick scratch (corner
+    // values, brick -> slot map, block counts and scans) and the per-active-brick one (active list,
+    // value store, point words, block counts and scans), both in 8-byte words
+    unsigned long long *d_spb = nullptr, *d_spa = nullptr;
+    size_t cap_spb = 0, cap_spa = 0;
 
     // settings
     float inv_view[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 2};
@@ -1155,7 +1160,7 @@ int nr_destroy(nr_ctx *c) {
     dfree(c->d_aas); dfree(c->d_aalist); dfree(c->d_aaacc);
     dfree(c->d_ls); dfree(c->d_lgbuf); dfree(c->d_lao);
     dfree(c->d_ps);
-    dfree(c->d_grid); dfree(c->d_mesh); dfree(c->d_mio);
+    dfree(c->d_grid); dfree(c->d_mesh); dfree(c->d_mio); dfree(c->d_spb); dfree(c->d_spa);
     if (c->h_frames) (void)hipHostFree(c->h_frames);
     if (c->ev_frames) (void)hipEventDestroy(c->ev_frames);
     if (c->h_ctr) (void)hipHostFree(c->h_ctr);
@@ -1851,6 +1856,178 @@ int nr_extract_mesh(nr_ctx *c, const float origin[3], const float step[3], const
         HIPCHK(c, hipStreamSynchronize(s));
         nr_stats st{};
         st.ray_steps = (uint64_t)L.n;
+        st.rays_shaded = (uint64_t)*nv;
+        st.shade_evals = with_normals ? 4ull * (uint64_t)*nv : 0ull;
+        st.launches = launches;
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        st.ms_total = ms;
+        *stats = st;
+    }
+    return NR_OK;
+}
+
+// ---- brick-sparse extraction (nr_sparse.hip) ----
+
+// ensure_buf for scratch whose size the lattice decides: a refused allocation is NR_E_NOMEM
+static int ensure_scratch(nr_ctx *c, const char *what, unsigned long long *&p, size_t &cap, size_t words) {
+    if (words <= cap) return NR_OK;
+    dfree(p);
+    cap = 0;
+    if (hipMalloc(&p, words * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        p = nullptr;
+        return set_err(c, NR_E_NOMEM, "nr_extract_mesh_sparse: cannot allocate %zu bytes of %s scratch", words * 8, what);
+    }
+    cap = words;
+    return NR_OK;
+}
+
+int nr_extract_mesh_sparse(nr_ctx *c, const float origin[3], const float step[3], const int dims[3], float iso, int brick,
+                           float band, float *vertices, float *normals, int64_t *keys, long v_cap, int32_t *triangles,
+                           long t_cap, long *nv, long *nt, long *active_bricks, int loc, nr_stats *stats) {
+    const char *fn = "nr_extract_mesh_sparse";
+    if (!c) return set_err(nullptr, NR_E_INVALID, "%s: ctx is NULL", fn);
+    if (!origin || !step || !dims || !nv || !nt) return set_err(c, NR_E_INVALID, "%s: NULL origin, step, dims, nv or nt", fn);
+    *nv = 0;
+    *nt = 0;
+    if (active_bricks) *active_bricks = 0;
+    for (int a = 0; a < 3; ++a)
+        if (dims[a] < 2 || dims[a] > 65536) return set_err(c, NR_E_INVALID, "%s: dims[%d] = %d outside 2..65536", fn, a, dims[a]);
+    if (brick != 4 && brick != 8 && brick != 16) return set_err(c, NR_E_INVALID, "%s: brick = %d is not 4, 8 or 16", fn, brick);
+    if (!(band >= 0.0f)) return set_err(c, NR_E_INVALID, "%s: band is negative or NaN", fn);
+    if (!std::isfinite(iso)) return set_err(c, NR_E_INVALID, "%s: iso is not finite", fn);
+    if (!vertices != !triangles) return set_err(c, NR_E_INVALID, "%s: vertices and triangles are given together", fn);
+    if ((keys || normals) && !vertices) return set_err(c, NR_E_INVALID, "%s: keys and normals need vertices", fn);
+    SparseArgs A{};
+    SparseLattice &L = A.L;
+    for (int a = 0; a < 3; ++a) { L.origin[a] = origin[a]; L.step[a] = step[a]; }
+    L.nx = dims[0]; L.ny = dims[1]; L.nz = dims[2];
+    L.B = brick; L.S = brick + 1;
+    L.nbx = (L.nx - 1 + brick - 1) / brick; L.nby = (L.ny - 1 + brick - 1) / brick; L.nbz = (L.nz - 1 + brick - 1) / brick;
+    const unsigned long long nbricks = (unsigned long long)L.nbx * L.nby * L.nbz;
+    if (nbricks > (1ull << 30)) return set_err(c, NR_E_INVALID, "%s: %llu bricks, more than 2^30", fn, nbricks);
+    int rc;
+    if ((rc = fused_check(c, fn)) != NR_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    L.nbricks = (uint32_t)nbricks;
+    L.ncoarse = (uint32_t)((unsigned long long)(L.nbx + 1) * (L.nby + 1) * (L.nbz + 1));  // < 2^32: at most 2^30 bricks of <= 2^14 an axis
+    L.P = (uint32_t)(L.S * L.S * L.S);
+    L.stride = (L.P + 63u) & ~63u;
+    L.inv_nbx = 1.0 / (double)L.nbx;
+    L.inv_nbxy = 1.0 / ((double)L.nbx * (double)L.nby);
+    L.inv_cx = 1.0 / (double)(L.nbx + 1);
+    L.inv_cxy = 1.0 / ((double)(L.nbx + 1) * (double)(L.nby + 1));
+    L.inv_s = 1.0 / (double)L.S;
+    L.inv_ss = 1.0 / (double)(L.S * L.S);
+    L.inv_wpb = 1.0 / (double)(L.stride >> 6);
+    A.iso = iso; A.band = band;
+    A.scene = c->scene; A.frame = c->frame;
+    // per-brick scratch, in 8-byte words: totals [2], scans [2][nblk], block counts [2][nblk] u32, the
+    // map [nbricks] i32, the corner values [ncoarse] f32
+    const size_t nblk_b = ((size_t)L.nbricks + 255) / 256;
+    if ((rc = ensure_scratch(c, "per-brick", c->d_spb, c->cap_spb,
+                             2 + 2 * nblk_b + nblk_b + ((size_t)L.nbricks + 1) / 2 + ((size_t)L.ncoarse + 1) / 2)) != NR_OK)
+        return rc;
+    A.nblk_b = (int)nblk_b;
+    A.btotal = c->d_spb;
+    A.boff = c->d_spb + 2;
+    A.bcnt = reinterpret_cast<uint32_t *>(c->d_spb + 2 + 2 * nblk_b);
+    A.map = reinterpret_cast<int32_t *>(c->d_spb + 2 + 3 * nblk_b);
+    A.coarse = reinterpret_cast<float *>(c->d_spb + 2 + 3 * nblk_b + ((size_t)L.nbricks + 1) / 2);
+    const int cus = num_cus(c->device);
+    const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : 12;  // as nr_sample_grid
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, launch_sparse_coarse(A, c->mlp16, (int)std::max<size_t>(1, std::min<size_t>(((size_t)L.ncoarse + 255) / 256, (size_t)cus * bpc)), s));
+    HIPCHK(c, launch_sparse_classify_count(A, s));
+    MeshArgs scan{};
+    scan.nblk = A.nblk_b; scan.cnt = A.bcnt; scan.off = A.boff; scan.total = A.btotal;
+    HIPCHK(c, launch_mesh_scan(scan, s));
+    int launches = 3;
+    unsigned long long btot[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(btot, A.btotal, sizeof btot, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    A.nactive = (uint32_t)btot[0];
+    if (active_bricks) *active_bricks = (long)btot[0];
+    unsigned long long mtot[2] = {0, 0};
+    const bool with_normals = normals && vertices;
+    if (A.nactive) {
+        // per-active-brick scratch: totals [2], scans [2][nblk], block counts [2][nblk] u32, the list
+        // [nactive] u32, the words and the values [nactive stride] u32 / f32
+        const size_t npts = (size_t)A.nactive * L.stride;
+        if (npts >= ((size_t)1 << 37))
+            return set_err(c, NR_E_NOMEM, "%s: %u active bricks need more than 1 TiB of scratch", fn, A.nactive);
+        const size_t nblk_m = (npts + 255) / 256;
+        if ((rc = ensure_scratch(c, "per-active-brick", c->d_spa, c->cap_spa,
+                                 2 + 2 * nblk_m + nblk_m + ((size_t)A.nactive + 1) / 2 + npts)) != NR_OK)
+            return rc;
+        A.nblk_m = (int)nblk_m;
+        A.total = c->d_spa;
+        A.off = c->d_spa + 2;
+        A.cnt = reinterpret_cast<uint32_t *>(c->d_spa + 2 + 2 * nblk_m);
+        A.list = reinterpret_cast<uint32_t *>(c->d_spa + 2 + 3 * nblk_m);
+        A.word = reinterpret_cast<uint32_t *>(c->d_spa + 2 + 3 * nblk_m + ((size_t)A.nactive + 1) / 2);
+        A.store = reinterpret_cast<float *>(A.word + npts);
+        HIPCHK(c, launch_sparse_classify_emit(A, s));
+        HIPCHK(c, launch_sparse_sample(A, c->mlp16, (int)std::max<size_t>(1, std::min<size_t>(nblk_m, (size_t)cus * bpc)), s));
+        HIPCHK(c, launch_sparse_mesh_count(A, s));
+        scan.nblk = A.nblk_m; scan.cnt = A.cnt; scan.off = A.off; scan.total = A.total;
+        HIPCHK(c, launch_mesh_scan(scan, s));
+        launches += 4;
+        HIPCHK(c, hipMemcpyAsync(mtot, A.total, sizeof mtot, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    *nv = (long)mtot[0];
+    *nt = (long)mtot[1];
+    if (mtot[0] > (unsigned long long)INT32_MAX)
+        return set_err(c, NR_E_INVALID, "%s: %llu vertices do not fit 32-bit indices", fn, mtot[0]);
+    if (vertices && (v_cap < *nv || t_cap < *nt))
+        return set_err(c, NR_E_NOMEM, "%s: %ld vertices / %ld triangles exceed the capacities %ld / %ld", fn, *nv, *nt,
+                       v_cap, t_cap);
+    if (vertices && mtot[0]) {
+        const size_t NV = (size_t)mtot[0], V3 = 3 * NV, T3 = 3 * (size_t)mtot[1];
+        float *dv = vertices, *dn = with_normals ? normals : nullptr;
+        int64_t *dk = keys;
+        int32_t *dt = triangles;
+        if (loc != NR_DEVICE) {
+            // staging: keys (8-byte aligned) first, then vertices, normals, triangles
+            if ((rc = ensure_buf(c, c->d_mio, c->cap_mio, (keys ? 2 * NV : 0) + V3 * (with_normals ? 2 : 1) + T3)) != NR_OK) return rc;
+            dk = keys ? reinterpret_cast<int64_t *>(c->d_mio) : nullptr;
+            dv = c->d_mio + (keys ? 2 * NV : 0);
+            dn = with_normals ? dv + V3 : nullptr;
+            dt = reinterpret_cast<int32_t *>(dv + V3 * (with_normals ? 2 : 1));
+        }
+        A.vertices = dv;
+        A.keys = reinterpret_cast<long long *>(dk);
+        A.triangles = dt;
+        HIPCHK(c, launch_sparse_mesh_emit(A, s));
+        launches += 1;
+        if (with_normals) {
+            VNormalArgs V{};
+            V.vertices = dv;
+            V.normals = dn;
+            V.nv = (long)NV;
+            V.scene = c->scene;
+            V.frame = c->frame;
+            const int vbpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : 4;  // as nr_extract_mesh
+            HIPCHK(c, launch_vnormal(V, c->mlp16, (int)std::max<size_t>(1, std::min<size_t>((NV + 63) / 64, (size_t)cus * vbpc)), s));
+            launches += 1;
+        }
+        if (loc != NR_DEVICE) {
+            HIPCHK(c, hipMemcpyAsync(vertices, dv, V3 * 4, hipMemcpyDeviceToHost, s));
+            if (with_normals) HIPCHK(c, hipMemcpyAsync(normals, dn, V3 * 4, hipMemcpyDeviceToHost, s));
+            if (keys) HIPCHK(c, hipMemcpyAsync(keys, dk, NV * 8, hipMemcpyDeviceToHost, s));
+            if (T3) HIPCHK(c, hipMemcpyAsync(triangles, dt, T3 * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+        }
+    }
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (stats) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        nr_stats st{};
+        st.ray_steps = (uint64_t)L.ncoarse + btot[1];
+        st.rays_hit = btot[0];
         st.rays_shaded = (uint64_t)*nv;
         st.shade_evals = with_normals ? 4ull * (uint64_t)*nv : 0ull;
         st.launches = launches;

@@ -167,6 +167,49 @@ bool pack_x3_32(const std::vector<int> &dims, const std::vector<std::vector<floa
                 const std::vector<std::vector<float>> &biases, std::vector<uint16_t> &a_ops, std::vector<float> &fl,
                 int *ok = nullptr);
 
+// ---- brick-sparse isosurface extraction (nr_sparse.hip; nr_extract_mesh_sparse) ----
+// The lattice and its bricks of B cells a side.  The values of an active brick's point set live in
+// a compact store: slot a of the active list (ascending brick index) owns the floats
+// [a * stride, a * stride + (B + 1)^3), local point (li, lj, lk) at (lk (B + 1) + lj)(B + 1) + li.
+// stride = (B + 1)^3 rounded up to a multiple of 64, so that a wave's 64 consecutive store points
+// belong to one brick.  A ragged brick (the last of an axis) uses the points up to its extent.
+struct SparseLattice {
+    float origin[3], step[3];
+    int nx, ny, nz;
+    int B, S;                     // brick edge in cells: 4, 8 or 16; S = B + 1
+    int nbx, nby, nbz;            // bricks per axis, ceil((dim - 1) / B)
+    uint32_t nbricks;             // nbx nby nbz <= 2^30
+    uint32_t ncoarse;             // (nbx + 1)(nby + 1)(nbz + 1): the brick-corner lattice
+    uint32_t P, stride;           // S^3 and its multiple of 64
+    double inv_nbx, inv_nbxy;     // reciprocals for udiv_r: the brick index,
+    double inv_cx, inv_cxy;       // the corner lattice (nbx + 1, (nbx + 1)(nby + 1)),
+    double inv_s, inv_ss;         // the local index (S, S^2)
+    double inv_wpb;               // and a wave's brick slot (stride / 64 waves per brick)
+};
+
+struct SparseArgs {
+    SparseLattice L;
+    float iso, band;
+    int scene, frame;
+    float *coarse;                // [ncoarse] the values at the brick corners
+    int32_t *map;                 // [nbricks] the brick's slot in the active list, -1: culled
+    int nblk_b;                   // ceil(nbricks / 256)
+    uint32_t *bcnt;               // [2][nblk_b]: active bricks, their point-set sizes, per 256 bricks
+    unsigned long long *boff;     // [2][nblk_b]: their exclusive scans
+    unsigned long long *btotal;   // [2]
+    uint32_t nactive;             // (read on the host once, after the classification)
+    uint32_t *list;               // [nactive] the active bricks, ascending
+    float *store;                 // [nactive][stride]
+    uint32_t *word;               // [nactive][stride]: as MeshArgs::word, over 256-point blocks of the store
+    int nblk_m;                   // ceil(nactive stride / 256)
+    uint32_t *cnt;                // [2][nblk_m]
+    unsigned long long *off;      // [2][nblk_m]
+    unsigned long long *total;    // [2]
+    float *vertices;              // [nv][3]
+    long long *keys;              // [nv] or null
+    int32_t *triangles;           // [nt][3]
+};
+
 // ---- context internals for nr_group.hip (nr_api.hip) ----
 int ctx_device(const nr_ctx *c);
 void *ctx_stream(nr_ctx *c);  // the hipStream_t the context's work runs on (creates its own stream if selected)

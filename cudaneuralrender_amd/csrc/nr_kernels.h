@@ -285,6 +285,15 @@ hipError_t launch_grid(const GridArgs &G, const MlpArgs &M, int grid, hipStream_
 hipError_t launch_vnormal(const VNormalArgs &V, const MlpArgs &M, int grid, hipStream_t st);
 hipError_t launch_mesh_count(const MeshArgs &A, hipStream_t st);  // k_mesh_count, then k_mesh_scan
 hipError_t launch_mesh_emit(const MeshArgs &A, hipStream_t st);
+hipError_t launch_mesh_scan(const MeshArgs &A, hipStream_t st);  // k_mesh_scan alone: reads nblk, cnt; writes off, total
+// nr_sparse.hip (SparseArgs: nr_internal.h)
+struct SparseArgs;
+hipError_t launch_sparse_coarse(const SparseArgs &A, const MlpArgs &M, int grid, hipStream_t st);
+hipError_t launch_sparse_classify_count(const SparseArgs &A, hipStream_t st);
+hipError_t launch_sparse_classify_emit(const SparseArgs &A, hipStream_t st);
+hipError_t launch_sparse_sample(const SparseArgs &A, const MlpArgs &M, int grid, hipStream_t st);
+hipError_t launch_sparse_mesh_count(const SparseArgs &A, hipStream_t st);
+hipError_t launch_sparse_mesh_emit(const SparseArgs &A, hipStream_t st);
 hipError_t launch_query(const QueryArgs &Q, const MlpArgs &M, int grid, hipStream_t st);
 hipError_t launch_aa_detect(const AaArgs &X, hipStream_t st);
 hipError_t launch_aa_trace(const RenderArgs &A, const AaArgs &X, const MlpArgs &M, int grid, hipStream_t st);  // 4-wave workgroups

@@ -211,6 +211,11 @@ hipError_t launch_mesh_count(const MeshArgs &A, hipStream_t st) {
     return hipGetLastError();
 }
 
+hipError_t launch_mesh_scan(const MeshArgs &A, hipStream_t st) {
+    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(1024), 0, st, A);
+    return hipGetLastError();
+}
+
 hipError_t launch_mesh_emit(const MeshArgs &A, hipStream_t st) {
     hipLaunchKernelGGL(k_mesh_emit, dim3(A.nblk), dim3(256), 0, st, A);
     return hipGetLastError();

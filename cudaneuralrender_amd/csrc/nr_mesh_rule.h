@@ -112,6 +112,24 @@ NR_MESH_HD uint32_t mesh_tet_mask(const MeshRule &R, uint32_t inside, int t) {
     return m;
 }
 
+// vmask and ntri of a point whose s, valid and inside are set
+NR_MESH_HD void mesh_point_masks(const MeshRule &R, MeshPoint &P) {
+    P.vmask = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int slot = 0; slot < 7; ++slot) {
+        const int b = MESH_SLOT_BITS[slot];
+        P.vmask |= ((P.valid >> b) & ((P.inside >> b) ^ P.inside) & 1u) << slot;
+    }
+    P.ntri = 0;
+    if ((P.valid >> 7) & 1u)
+        for (int t = 0; t < 6; ++t) {
+            const int pc = __builtin_popcount(mesh_tet_mask(R, P.inside, t));
+            P.ntri += pc == 2 ? 2u : (pc == 1 || pc == 3) ? 1u : 0u;
+        }
+}
+
 NR_MESH_HD MeshPoint mesh_point(const MeshRule &R, const float *sdf, uint32_t p, int i, int j, int k, int nx, int ny,
                                 int nz, float iso) {
     MeshPoint P;
@@ -129,20 +147,7 @@ NR_MESH_HD MeshPoint mesh_point(const MeshRule &R, const float *sdf, uint32_t p,
         P.valid |= (uint32_t)ok << c;
         P.inside |= (uint32_t)(ok && s < iso) << c;
     }
-    P.vmask = 0;
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-    for (int slot = 0; slot < 7; ++slot) {
-        const int b = MESH_SLOT_BITS[slot];
-        P.vmask |= ((P.valid >> b) & ((P.inside >> b) ^ P.inside) & 1u) << slot;
-    }
-    P.ntri = 0;
-    if ((P.valid >> 7) & 1u)
-        for (int t = 0; t < 6; ++t) {
-            const int pc = __builtin_popcount(mesh_tet_mask(R, P.inside, t));
-            P.ntri += pc == 2 ? 2u : (pc == 1 || pc == 3) ? 1u : 0u;
-        }
+    mesh_point_masks(R, P);
     return P;
 }
 

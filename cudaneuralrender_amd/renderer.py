@@ -624,6 +624,65 @@ class Renderer:
             out["normals"] = N
         return (out, st.as_dict()) if with_stats else out
 
+    def _sparse_band(self, step, brick, band):
+        """band=None: the brick's diagonal, computed in double and rounded to f32 -- the bound that is
+        sound for a field with gradient at most 1."""
+        if band is not None:
+            return float(band)
+        return float(np.float32(np.sqrt(sum((float(brick) * float(x)) ** 2 for x in step))))
+
+    def extract_mesh_sparse(self, origin, step, dims, iso=0.0, brick=8, band=None, normals=True, keys=True,
+                            with_stats=False):
+        """nr_extract_mesh_sparse: nr_extract_mesh restricted to the bricks of brick^3 cells that have
+        a corner within `band` of iso (or a sign change, or a NaN) -- for lattices too large to sample
+        densely.  band=None is the brick's diagonal; too small a band leaves holes.  Returns a dict with
+        "vertices" [nv, 3] float32, "triangles" [nt, 3] int32, "active_bricks" and, as asked, "normals"
+        [nv, 3] and "keys" [nv] int64 (index * 7 + slot: np.argsort(keys) is the dense mesh's vertex
+        order).  The count-only call comes first, then the buffers are allocated."""
+        o, s, d = _lattice(origin, step, dims)
+        bandf = self._sparse_band(s, brick, band)
+        nv, nt, na = ctypes.c_long(0), ctypes.c_long(0), ctypes.c_long(0)
+        st = NRStats()
+
+        def call(V, N, K, T):
+            return self._L.nr_extract_mesh_sparse(
+                self._ctx, _fptr(o), _fptr(s), d, float(iso), int(brick), bandf,
+                None if V is None else V.ctypes.data, None if N is None else N.ctypes.data,
+                None if K is None else K.ctypes.data, 0 if V is None else V.shape[0],
+                None if T is None else T.ctypes.data, 0 if T is None else T.shape[0],
+                ctypes.byref(nv), ctypes.byref(nt), ctypes.byref(na), NR_HOST, ctypes.byref(st) if with_stats else None)
+
+        self._chk(call(None, None, None, None))
+        V, T = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
+        N = np.zeros((nv.value, 3), np.float32) if normals else None
+        K = np.zeros((nv.value,), np.int64) if keys else None
+        if nv.value:
+            self._chk(call(V, N, K, T))
+        out = {"vertices": V, "triangles": T, "active_bricks": na.value}
+        if normals:
+            out["normals"] = N
+        if keys:
+            out["keys"] = K
+        return (out, st.as_dict()) if with_stats else out
+
+    def extract_mesh_sparse_device(self, origin, step, dims, vertices_ptr, v_cap, triangles_ptr, t_cap, iso=0.0, brick=8,
+                                   band=None, normals_ptr=None, keys_ptr=None, with_stats=False):
+        """nr_extract_mesh_sparse into device buffers (e.g. torch tensors' data_ptr(): v_cap x 3
+        float32 vertices and normals, v_cap int64 keys, t_cap x 3 int32 triangles; both vertices_ptr
+        and triangles_ptr None: count only), on the context's stream (set_stream).  Returns
+        (nv, nt, active_bricks), with the stats dict appended with_stats=True; short capacities raise
+        NRError with nothing written."""
+        o, s, d = _lattice(origin, step, dims)
+        vp = [ctypes.c_void_p(p) if p else None for p in (vertices_ptr, normals_ptr, keys_ptr, triangles_ptr)]
+        nv, nt, na = ctypes.c_long(0), ctypes.c_long(0), ctypes.c_long(0)
+        st = NRStats()
+        self._chk(self._L.nr_extract_mesh_sparse(
+            self._ctx, _fptr(o), _fptr(s), d, float(iso), int(brick), self._sparse_band(s, brick, band), vp[0], vp[1], vp[2],
+            int(v_cap), vp[3], int(t_cap), ctypes.byref(nv), ctypes.byref(nt), ctypes.byref(na), NR_DEVICE,
+            ctypes.byref(st) if with_stats else None))
+        res = (nv.value, nt.value, na.value)
+        return res + (st.as_dict(),) if with_stats else res
+
     def mlp_forward(self, X):
         X = np.ascontiguousarray(X, np.float32)
         info = self.mlp_info()

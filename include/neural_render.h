@@ -378,6 +378,67 @@ int nr_mesh_grid(nr_ctx *ctx, const float *sdf /*[nz][ny][nx]*/, const float ori
 int nr_extract_mesh(nr_ctx *ctx, const float origin[3], const float step[3], const int dims[3], float iso,
                     float *vertices /*[v_cap][3]*/, float *normals /*[v_cap][3] or NULL*/, long v_cap,
                     int32_t *triangles /*[t_cap][3]*/, long t_cap, long *nv, long *nt, int loc, nr_stats *stats);
+/* nr_extract_mesh on a lattice too large to sample densely: the lattice is cut into bricks of
+ * `brick`^3 cells, the scene is sampled at the brick corners, and only the bricks the surface can
+ * reach are sampled and meshed.  The mesh is nr_mesh_grid's mesh of the full lattice restricted to
+ * those bricks, bit for bit.
+ *  1. Lattice.  That of nr_sample_grid (index (k * ny + j) * nx + i, coordinate origin[a] +
+ *     (float)idx_a * step[a]), every dim 2..65,536; nx * ny * nz is not limited to 2^30, and linear
+ *     indices and keys are 64-bit.
+ *  2. Bricks.  brick = B in {4, 8, 16}.  Axis a has nb_a = ceil((dims[a] - 1) / B) bricks; brick
+ *     (bx, by, bz) has linear index (bz * nby + by) * nbx + bx and covers, along axis a, the cells
+ *     B b_a .. min(B b_a + B, dims[a] - 1) - 1 (the last brick of an axis may be ragged, 1..B cells).
+ *     Its point set is the lattice points B b_a .. min(B b_a + B, dims[a] - 1) per axis, its 8
+ *     corners the extreme points of that set.  nbx * nby * nbz <= 2^30.
+ *  3. Values.  Every value used is sceneSDF(p, mlp(p)) at a lattice point, with nr_sample_grid's
+ *     bits for that point: the coordinate comes from the global index as in 1, never from a brick
+ *     origin plus an offset.  Always the fp32 MLP with the context's scene and frame;
+ *     nr_set_precision and nr_set_schedule are ignored, and the call leaves the context's settings
+ *     as it found them.
+ *  4. Active bricks.  With d = fabsf(s - iso) (one f32 subtract) for a corner value s, a brick is
+ *     active iff a corner value is NaN, or its corners differ in insideness (inside: s < iso, as
+ *     nr_mesh_grid), or the smallest d of its corners is <= band.  band >= 0; +INFINITY makes every
+ *     brick active.
+ *  5. Mesh.  Triangles: exactly those nr_mesh_grid's rule gives for the cells of active bricks.
+ *     Vertices: exactly the crossing lattice edges (o, slot) whose two ends both lie in the point
+ *     set of some active brick (each is an edge of a Kuhn tetrahedron of a cell of that brick); one
+ *     vertex per edge however many bricks share it, at nr_mesh_grid's position, bit for bit.
+ *     keys[v] = index(o) * 7 + slot with the 64-bit linear index of o -- the number that orders the
+ *     dense mesh's vertices, so a caller can sort into the dense order or stitch tiles.  normals as
+ *     nr_extract_mesh.  vertices, normals and keys share one order; that order, the triangle order
+ *     and the vertex a triangle starts with are fixed -- the same bytes on every call for the same
+ *     inputs, at any grid size or occupancy, no atomic deciding an order -- but not otherwise
+ *     specified.  The windings are nr_mesh_grid's.  With band = +INFINITY the mesh sorted by key is
+ *     nr_extract_mesh's; with a band for which every crossing cell lies in an active brick it is
+ *     that mesh too, closed wherever the dense one is.
+ *     What it is not: a proof that nothing was culled.  The band is sound when the field changes by
+ *     at most `band` over a brick's diagonal; a network is only approximately a distance field, and
+ *     too small a band silently leaves holes at the culled bricks.
+ *  6. Capacities.  As nr_mesh_grid: *nv and *nt are always set, *active_bricks when given; with
+ *     vertices == NULL && triangles == NULL the call only counts; if a capacity is short nothing is
+ *     written and the call returns NR_E_NOMEM.  keys and normals need vertices.  At most 2^31 - 1
+ *     vertices.  loc applies to every pointer but nv, nt and active_bricks.
+ *  7. Stats (may be NULL).  ray_steps = (nbx + 1)(nby + 1)(nbz + 1) plus the sum over the active
+ *     bricks of their point-set sizes (a point shared by neighbouring active bricks counts once per
+ *     brick: it is evaluated in each, to the same bits); rays_hit = active bricks; rays_shaded =
+ *     *nv; shade_evals = 4 * *nv with normals, else 0; launches and ms_total as elsewhere.
+ *  8. Errors.  NR_E_INVALID: a NULL ctx, origin, step, dims, nv or nt; a dim outside 2..65,536;
+ *     brick not 4, 8 or 16; band negative or NaN; iso not finite; only one of vertices / triangles
+ *     given; keys or normals without vertices; more than 2^30 bricks.  NR_E_STATE: no network.
+ *     NR_E_FORMAT: a network the fused kernels do not take.  NR_E_NOMEM: short capacities, or scratch
+ *     that cannot be allocated (the message through nr_last_error).
+ *  9. Scratch.  The context owns it and keeps it until nr_destroy.  Per brick: 4 bytes (the brick ->
+ *     slot map) + 4 bytes per point of the brick-corner lattice + 24 bytes per 256 bricks.  Per
+ *     active brick: 4 bytes (the active list) + 8 bytes (value, pass word) per active point -- the
+ *     brick's (B + 1)^3 points rounded up to a multiple of 64: 128, 768 or 4,928 -- + 24 bytes per
+ *     256 active points.  For loc = NR_HOST also staging of the mesh's size.  The active-brick count is read on the host once, before the per-brick store is
+ *     sized (as nr_render_aa reads its edge count). */
+int nr_extract_mesh_sparse(nr_ctx *ctx, const float origin[3], const float step[3], const int dims[3],
+                           float iso, int brick, float band,
+                           float *vertices /*[v_cap][3]*/, float *normals /*[v_cap][3] or NULL*/,
+                           int64_t *keys /*[v_cap] or NULL*/, long v_cap,
+                           int32_t *triangles /*[t_cap][3]*/, long t_cap,
+                           long *nv, long *nt, long *active_bricks /*or NULL*/, int loc, nr_stats *stats);
 /* Wavefront OBJ writer (host only, host pointers): "v x y z" per vertex and, when normals is given,
  * "vn x y z", printed with %.9g (which round-trips f32); faces "f a b c", or "f a//a b//b c//c" with
  * normals, 1-based.  NR_E_IO when the file cannot be opened or written. */
