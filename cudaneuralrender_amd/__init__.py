@@ -11,7 +11,7 @@ from ._lib import (LIB_PATH, NR_ENDGAME_DEFAULT, NR_PRECISION, NR_RAY_ESCAPED, N
 from ._lib import NR_AA_CONTRAST_DEFAULT, NR_AA_MODE, NRLight  # noqa: F401
 from ._lib import NR_PROJ_CONVERGED, NR_PROJ_FLAT, NR_PROJ_LIMIT, NRProjectOpts  # noqa: F401
 from .renderer import (NR_COLOR_FACING, NR_COLOR_MATCAP, Group, Renderer, assemble_shards, camera,  # noqa: F401
-                       load_png, pack_fp32_pruned, pack_x3, read_keras_h5, save_obj, save_png, save_ppm, shard_rows, batch_frames_per_launch,
+                       load_png, pack_fp32_pruned, pack_fp32_units, pack_x3, read_keras_h5, save_obj, save_png, save_ppm, shard_rows, batch_frames_per_launch,
                        group_layout)
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))

@@ -44,6 +44,7 @@ EXPORTS = [
     "nr_sample_grid", "nr_mesh_grid", "nr_extract_mesh", "nr_extract_mesh_sparse", "nr_obj_save",
     "nr_mlp_gradient", "nr_project_points",
     "nr_pack_fp32_pruned", "nr_set_prune", "nr_prune_info", "nr_prune_redos",
+    "nr_set_unit_skip", "nr_unit_skip_counts", "nr_pack_fp32_units",
 ]
 
 
@@ -205,6 +206,10 @@ def lib():
         "nr_set_prune": (I, [P, I]),
         "nr_prune_info": (I, [P, IP, IP, IP, IP, I]),
         "nr_prune_redos": (I, [P, ctypes.POINTER(ctypes.c_ulonglong)]),
+        "nr_set_unit_skip": (I, [P, I]),
+        "nr_unit_skip_counts": (I, [P, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
+        "nr_pack_fp32_units": (I, [I, IP, ctypes.POINTER(FP), ctypes.POINTER(FP), FP, ctypes.c_long,
+                                   ctypes.POINTER(ctypes.c_long), IP]),
         "nr_set_occupancy": (I, [P, I]),
         "nr_set_pixel_spread": (I, [P, I]),
         "nr_set_cost_probe": (I, [P, I, I]),

@@ -64,6 +64,8 @@ struct nr_ctx {
     float *d_pkp = nullptr;     // the pruned fp32 pack (pack_fp32_16_pruned; the batched fp32 k_trace), null: none
     PruneInfo prune;            // its order and k-steps (nrelu = 0: none)
     int prune_mode = 1;         // nr_set_prune
+    float *d_pku = nullptr;     // the unit pack (pack_fp32_units; the batched fp32 k_trace), null: refused
+    int unit_skip = 1;          // nr_set_unit_skip
     int schedule = 0; // NR_SCHED_PERSISTENT
     uint32_t *d_tr = nullptr;  // persistent-schedule counters + stats
     int debug = 0;
@@ -252,7 +254,7 @@ int free_network(nr_ctx *c) {
     for (auto *p : c->d_W) (void)hipFree(p);
     for (auto *p : c->d_b) (void)hipFree(p);
     c->d_W.clear(); c->d_b.clear();
-    dfree(c->d_pack16); dfree(c->d_pkp); dfree(c->d_gpack16); dfree(c->d_lp16); dfree(c->d_lpf16); dfree(c->d_x3lp); dfree(c->d_x3fl);
+    dfree(c->d_pack16); dfree(c->d_pkp); dfree(c->d_pku); dfree(c->d_gpack16); dfree(c->d_lp16); dfree(c->d_lpf16); dfree(c->d_x3lp); dfree(c->d_x3fl);
     dfree(c->d_lps16); dfree(c->d_lpfs16);
     c->fused = false;
     if (c->lgraph) { (void)hipGraphExecDestroy(c->lgraph); c->lgraph = nullptr; }
@@ -333,13 +335,27 @@ int upload_lowp(nr_ctx *c) {
 
 // The pruned fp32 pack for c->prune_mode beside the full one (same size); MlpArgs::pkp only while
 // the clamped form is on (nr_set_debug bit 9 turns both off).
+// MlpArgs::pku: the unit form runs while unit skip is on, the prune mode is 1 and the clamped form
+// is on; nr_set_prune 0 and 2 and nr_set_unit_skip(0) keep the paths they had
+void select_unit_pack(nr_ctx *c) {
+    c->mlp16.pku = c->unit_skip && c->prune_mode == 1 && c->mlp16.f32_clamp ? c->d_pku : nullptr;
+}
+
 int upload_pruned(nr_ctx *c) {
     dfree(c->d_pkp);
+    dfree(c->d_pku);
     c->prune = PruneInfo{};
     c->mlp16.pkp = nullptr;
+    c->mlp16.pku = nullptr;
     c->mlp16.ks_bits = 0;
     if (!c->fused) return NR_OK;
     std::vector<float> pp;
+    if (pack_fp32_units(c->dims, c->kernels, c->biases, pp)) {
+        pp.resize((size_t)c->mlp16.pk_bytes / 4, 0.0f);
+        HIPCHK(c, hipMalloc(&c->d_pku, (size_t)c->mlp16.pk_bytes));
+        HIPCHK(c, hipMemcpy(c->d_pku, pp.data(), (size_t)c->mlp16.pk_bytes, hipMemcpyHostToDevice));
+    }
+    select_unit_pack(c);
     if (!pack_fp32_16_pruned(c->dims, c->kernels, c->biases, c->prune_mode, pp, c->prune)) {
         c->prune = PruneInfo{};
         return NR_OK;
@@ -611,9 +627,9 @@ int order_buffers(nr_ctx *c, int W, int H, int band, int nshards, int shard, int
 
 // ---- the persistent tracer's launch (k_trace), shared by its single-frame and batched drivers ----
 
-// d_tr: one set of NR_MAX_QUEUES shard counters on their own 128-byte lines, then 8 x u64 stats
+// d_tr: one set of NR_MAX_QUEUES shard counters on their own 128-byte lines, then 16 x u64 stats
 // (allocated twice over: the cost probe's launch has a set of its own)
-constexpr size_t TR_BYTES = NR_MAX_QUEUES * 128 + 8 * 8;
+constexpr size_t TR_BYTES = NR_MAX_QUEUES * 128 + 16 * 8;
 
 inline uint64_t lane_cap_for(int take) { return take >= 64 ? ~0ull : (1ull << take) - 1ull; }
 
@@ -2468,6 +2484,7 @@ int nr_set_debug(nr_ctx *c, int flags) {
     c->mlp16.lp_clamp = c->clamp_ok && !c->no_clamp && c->mlp16.lp != nullptr;
     c->mlp16.f32_clamp = c->f32_clamp_ok && !c->no_clamp;
     c->mlp16.pkp = c->mlp16.f32_clamp ? c->d_pkp : nullptr;
+    select_unit_pack(c);
     return NR_OK;
 }
 
@@ -2506,6 +2523,48 @@ int nr_prune_redos(nr_ctx *c, unsigned long long *redos) {
     HIPCHK(c, hipStreamSynchronize(s));
     HIPCHK(c, hipMemcpy(redos, reinterpret_cast<unsigned long long *>(c->d_tr + NR_MAX_QUEUES * 32) + 6, 8,
                         hipMemcpyDeviceToHost));
+    return NR_OK;
+}
+
+int nr_set_unit_skip(nr_ctx *c, int on) {
+    if (!c) return set_err(nullptr, NR_E_INVALID, "ctx is NULL");
+    c->unit_skip = on != 0;
+    select_unit_pack(c);
+    return NR_OK;
+}
+
+int nr_unit_skip_counts(nr_ctx *c, unsigned long long *issued, unsigned long long *skipped) {
+    if (!c || !issued || !skipped) return set_err(c, NR_E_INVALID, "nr_unit_skip_counts: NULL argument");
+    *issued = *skipped = 0;
+    if (!c->d_tr || c->dims.empty()) return NR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    HIPCHK(c, hipStreamSynchronize(s));
+    unsigned long long h[2] = {0, 0};  // [7] skipped, [8] wave evaluations of the unit form
+    HIPCHK(c, hipMemcpy(h, reinterpret_cast<unsigned long long *>(c->d_tr + NR_MAX_QUEUES * 32) + 7, sizeof h,
+                        hipMemcpyDeviceToHost));
+    *skipped = h[0];
+    *issued = h[1] * (unsigned long long)(c->mlp16.in0 + 32 * c->mlp16.nh);
+    return NR_OK;
+}
+
+int nr_pack_fp32_units(int nlayers, const int *dims, const float *const *kernels, const float *const *biases, float *pack,
+                       long cap, long *len, int *has_pack) {
+    if (nlayers < 1 || !dims || !kernels || !biases || !len || !has_pack)
+        return nr::report_error(NR_E_INVALID, "nr_pack_fp32_units: bad arguments");
+    std::vector<int> d(dims, dims + nlayers + 1);
+    std::vector<std::vector<float>> K(nlayers), B(nlayers);
+    for (int l = 0; l < nlayers; ++l) {
+        if (!kernels[l] || !biases[l] || d[l] < 1 || d[l + 1] < 1)
+            return nr::report_error(NR_E_INVALID, "nr_pack_fp32_units: layer %d", l);
+        K[l].assign(kernels[l], kernels[l] + (size_t)d[l] * d[l + 1]);
+        B[l].assign(biases[l], biases[l] + d[l + 1]);
+    }
+    std::vector<float> pv;
+    const bool hp = pack_fp32_units(d, K, B, pv);
+    *has_pack = hp ? 1 : 0;
+    *len = hp ? (long)pv.size() : 0;
+    if (hp && pack && cap >= (long)pv.size()) std::memcpy(pack, pv.data(), pv.size() * 4);
     return NR_OK;
 }
 

@@ -146,6 +146,20 @@ inline unsigned long long prune_ks_bits(const PruneInfo &p) {
     for (int l = 0; l < p.nrelu; ++l) b |= (unsigned long long)(p.ks[l] - 4) << (3 * l);
     return b;
 }
+// The unit pack (the batched fp32 k_trace; nr_mlp16.h mlp64_fp32_units): the scaled pack's values
+// (clamp_scales / apply_scales as pack_fp32_16, bit for bit) in identity unit order, pk_floats(nh)
+// floats like the others:
+//   [0,128)    layer-0 weights     [input 4][row 32]          (0 for input >= dims[0]; unscaled)
+//   [128,160)  layer-0 bias        [row 32]
+//   per hidden layer j (0..nh-1), base 160 + j*1056:
+//              weights             [k >> 2][row 32][k & 3]    (k = input unit: a lane reads four
+//                                                              consecutive k of its row at once)
+//              bias                [row 32]
+//   final:     weights [unit 32], bias [1], layer-0 output scale 2^-e0 [1] (+2 pad)
+// False (no pack) if the shape is not fused, the scaled pack is refused, a weight or bias is not
+// finite, or a bias is -0 (the exactness argument in nr_mlp16.h).
+bool pack_fp32_units(const std::vector<int> &dims, const std::vector<std::vector<float>> &kernels,
+                     const std::vector<std::vector<float>> &biases, std::vector<float> &pack);
 // the backward pack (above); false if the shape is not fused or has more than GRAD_MAX_HIDDEN
 // hidden 32 x 32 layers
 bool pack_grad_16(const std::vector<int> &dims, const std::vector<std::vector<float>> &kernels,

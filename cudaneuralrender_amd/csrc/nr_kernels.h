@@ -47,6 +47,10 @@ struct MlpArgs {
                             // it stages in LDS instead of pk; null: none (the scaled pack was refused, or
                             // f32_clamp is off) -- it then stages pk and runs the add + max form
     unsigned long long ks_bits;  // pkp: k-steps per ReLU layer, ks[l] - 4 in bits [3l, 3l + 3)
+    const float *pku;       // the batched fp32 k_trace: the unit pack (nr_internal.h pack_fp32_units), which it
+                            // stages in LDS instead of pkp / pk for the one-MFMA-per-unit form
+                            // (nr_mlp16.h mlp64_fp32_units); null: off (nr_set_unit_skip, nr_set_prune 0 or 2),
+                            // or the pack was refused
 };
 
 // Per-render constants (the reference's __constant__ state, volumeRender_kernel.cu:31-35,
@@ -126,7 +130,9 @@ struct TraceArgs {
     int nq_shift;
     unsigned long long *stats;  // [0] ray-steps, [1] rays hit, [2] max iterations, [3] rays shaded,
                                 // [4] fp32x3 march evaluations (the endgame), [5] rays handed to it,
-                                // [6] wave evaluations redone on the full fp32 pack (MlpArgs::pkp)
+                                // [6] wave evaluations redone on the full fp32 pack (MlpArgs::pkp),
+                                // [7] unit instructions skipped, [8] wave evaluations of the unit form
+                                // (MlpArgs::pku)
     unsigned long long *stamps; // diagnostics (nr_set_debug): per wave {start, queue drained, end, ray-steps}
     // pixel queue over 8x8 pixel blocks of the shard image, dispensed in `order`
     // (NULL = raster order); bcost (may be NULL) receives each block's max ray iterations

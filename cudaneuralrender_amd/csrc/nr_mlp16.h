@@ -496,6 +496,141 @@ __device__ __forceinline__ float mlp16_fp32_pruned(const MlpArgs &M, const float
     return mlp16_fp32_nt<4>(s, M.in0, M.nh, fr, x, y, z);
 }
 
+// ---- the clamped fp32 MLP, one MFMA per hidden unit (nr_internal.h pack_fp32_units; the batched fp32 k_trace) ----
+//
+// v_mfma_f32_32x32x1_2b_f32 has K = 1 and two 32-column blocks: one instruction applies one input
+// unit to all 32 output units (rows) of all 64 points of the wave -- point p in lane p: block
+// p / 32, column p % 32.  A = the unit's weight of row lane % 32 (the same in both halves), B = the
+// lane's own activation of that unit.  It is one fmaf per element, so a layer's chain is the
+// instructions in program order, units ascending: the oracle's order, with no re-ordering, no
+// candidates and no redo.  The instruction of a unit whose activation is +0 in every live lane is
+// skipped behind a scalar branch.
+//
+// Exactness.  A skipped unit drops the terms fma(w, +0, acc) from the chains of the live lanes,
+// which is the argument of the pruned form above: the chains end equal or as zeros of different
+// sign, and the bias add (no bias is -0, every weight finite: the pack is refused otherwise) maps
+// those to the same bits.  Only +0 is dropped: the test is on the activation's bit pattern, so a
+// -0 or a NaN (neither can come out of the clamp) would be issued, never skipped.  Unit 0 of a
+// layer is always issued, on a zero C operand: fma(w, +0, +0) = +0, and the accumulators need no
+// zeroing.  Lanes outside `live` hold stale points: they cannot block a skip, and their results,
+// which a skip may change, are not read.
+//
+// D layout (tools/mfma_peak.hip checks it): register r of lane l holds block r / 16, column l % 32,
+// row (r % 4) + 8 (r % 16 / 4) + 4 (l / 32).  The bias add and clamp run on that layout (bias of the
+// lane's rows: four ds_read_b128); then 16 v_permlane32_swap (register r of the upper half with
+// register 16 + r of the lower half) leave every lane with the 32 activations of its own point,
+// unit u in register unit_reg(u), ready to be the next layer's B operands.  The final 32 -> 1 layer
+// is an fmaf chain in the lane, units ascending, then the bias.
+//
+// Cost (profiles/unit_skip_peak.txt): 64 cycles per issued unit, the 16x16x4 rate; about 8.5
+// cycles per tested unit when a group's tests precede its branches (15 with test and branch
+// alternating), about 10 per v_permlane32_swap.
+// units per group of tests, 4 or 8: a group's tests come before its branches.  8 measured 4 % faster
+// than 4 on the headline (profiles/unit_skip_bench.txt), within the same registers
+#ifndef NR_UNIT_GROUP
+#define NR_UNIT_GROUP 8
+#endif
+typedef float f32x32 __attribute__((ext_vector_type(32)));
+__device__ __forceinline__ constexpr int unit_reg(int u) { return 16 * ((u >> 2) & 1) + (u & 3) + 4 * (u >> 3); }
+
+// the epilogue of a layer: c (D layout) -> a (every lane its own point's activations)
+template <bool L0>
+__device__ __forceinline__ void units_epilogue(const f32x32 &c, f32x32 &a, const float *bias, float s0, int h) {
+    const float4 *bb = reinterpret_cast<const float4 *>(bias + 4 * h);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 b4 = bb[2 * q];  // rows 8q + 4h .. + 3
+        const float b[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = 4 * q + i;
+            // (layer 0: its weights are unscaled; fma(c, 2^-e0, b 2^-e0) = (c + b) 2^-e0 in one rounding)
+            a[r] = __builtin_amdgcn_fmed3f(L0 ? __builtin_fmaf(c[r], s0, b[i]) : c[r] + b[i], 0.0f, 1.0f);
+            a[16 + r] = __builtin_amdgcn_fmed3f(L0 ? __builtin_fmaf(c[16 + r], s0, b[i]) : c[16 + r] + b[i], 0.0f, 1.0f);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        auto t = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[r]), __float_as_uint(a[16 + r]), false, false);
+        a[r] = __uint_as_float(t[0]);
+        a[16 + r] = __uint_as_float(t[1]);
+    }
+}
+
+// nskip: the wave's count of skipped instructions (wave-uniform)
+__device__ __forceinline__ float mlp64_fp32_units(const float *__restrict__ s, int in0, int nh, float fr, float x, float y,
+                                                  float z, unsigned long long live, uint32_t &nskip) {
+    // (an opaque copy of the lane index: the addresses derived from it are then formed here, not
+    // hoisted out of the tracer's loop into registers held for the kernel's life)
+    int lane = lane_id();
+    asm volatile("" : "+v"(lane));
+    const int row = lane & 31, h = lane >> 5;
+    f32x32 a, c;
+    {
+        const float *w = s + PK_L0W + row;
+        c = __builtin_amdgcn_mfma_f32_32x32x1f32(w[0], x, f32x32{}, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x1f32(w[32], y, c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x1f32(w[64], z, c, 0, 0, 0);
+        if (in0 == 4) c = __builtin_amdgcn_mfma_f32_32x32x1f32(w[96], fr, c, 0, 0, 0);
+        units_epilogue<true>(c, a, s + PK_L0B, s[pk_final(nh) + 33], h);
+    }
+    uint32_t ni = 0;  // instructions issued behind a branch
+    constexpr int UG = NR_UNIT_GROUP;  // units per group of tests: 4 or 8
+    for (int jl = 0; jl < nh; ++jl) {
+        const float *L = s + PK_HID + jl * PK_HID_STRIDE;
+        const float4 *W4 = reinterpret_cast<const float4 *>(L) + row;
+#pragma unroll
+        for (int g = 0; g < 32 / UG; ++g) {  // units UG g .. UG g + UG - 1: their tests first, then a branch each
+            float w[UG];
+#pragma unroll
+            for (int q = 0; q < UG / 4; ++q) {
+                const float4 wv = W4[(UG / 4 * g + q) * 32];
+                w[4 * q] = wv.x; w[4 * q + 1] = wv.y; w[4 * q + 2] = wv.z; w[4 * q + 3] = wv.w;
+            }
+            unsigned long long m[UG];
+#pragma unroll
+            for (int i = 0; i < UG; ++i) {
+                m[i] = __builtin_amdgcn_ballot_w64(__float_as_uint(a[unit_reg(UG * g + i)]) != 0u) & live;
+            }
+#pragma unroll
+            for (int i = 0; i < UG; ++i) {
+                const int u = UG * g + i;
+                if (u == 0) c = __builtin_amdgcn_mfma_f32_32x32x1f32(w[i], a[unit_reg(u)], f32x32{}, 0, 0, 0);
+                else if (m[i]) {
+                    c = __builtin_amdgcn_mfma_f32_32x32x1f32(w[i], a[unit_reg(u)], c, 0, 0, 0);
+                    ++ni;  // (a scalar add beside the instruction: no else)
+                }
+            }
+        }
+        units_epilogue<false>(c, a, L + 1024, 0.0f, h);
+    }
+    nskip += 31u * (uint32_t)nh - ni;
+    const float4 *wf4 = reinterpret_cast<const float4 *>(s + pk_final(nh));
+    float acc = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const float4 wv = wf4[q];
+        acc = __builtin_fmaf(wv.x, a[unit_reg(4 * q + 0)], acc);
+        acc = __builtin_fmaf(wv.y, a[unit_reg(4 * q + 1)], acc);
+        acc = __builtin_fmaf(wv.z, a[unit_reg(4 * q + 2)], acc);
+        acc = __builtin_fmaf(wv.w, a[unit_reg(4 * q + 3)], acc);
+    }
+    return acc + s[pk_final(nh) + 32];
+}
+
+// The batched fp32 tracer's MLP while M.pku is set (s: the unit pack, staged in LDS): waves whose
+// inputs are within the bound take the form above (neval counts them); a wave with an input beyond
+// it takes the add + max form on all four tiles of the full pack from global memory, as the pruned
+// form's redo does.
+__device__ __forceinline__ float mlp64_fp32_units(const MlpArgs &M, const float *s, float fr, float x, float y, float z,
+                                                  unsigned long long live, uint32_t &nskip, uint32_t &neval) {
+    if (inputs_in_bound_f32(x, y, z, fr)) {
+        ++neval;
+        return mlp64_fp32_units(s, M.in0, M.nh, fr, x, y, z, live, nskip);
+    }
+    return mlp16_fp32_nt<4>((const float *)(const __attribute__((address_space(1))) float *)M.pk, M.in0, M.nh, fr, x, y, z);
+}
+
 // bf16 / fp16: the whole MLP on 32-point tiles, v_mfma_f32_32x32x16_{bf16,f16} (nr_internal.h
 // LP32_*).  The wave's 64 points form two tiles (points 0-31, 32-63); in a tile, lane l
 // feeds point l & 31 and the k-slots 8h..8h+7 of its half h = l >> 5.

@@ -286,6 +286,38 @@ bool pack_fp32_16(const std::vector<int> &dims, const std::vector<std::vector<fl
     return true;
 }
 
+// ---- the unit pack (nr_internal.h; nr_mlp16.h mlp64_fp32_units) ----
+bool pack_fp32_units(const std::vector<int> &dims, const std::vector<std::vector<float>> &Kin,
+                     const std::vector<std::vector<float>> &Bin, std::vector<float> &pack) {
+    if (!fused_shape_ok(dims)) return false;
+    const int nl = (int)dims.size() - 1, nh = nl - 2, in0 = dims[0];
+    std::vector<int> e;
+    if (!clamp_scales(dims, Kin, Bin, e, (double)F32_INPUT_BOUND, 1, 0x1p-19)) return false;
+    // finite weights (0 x inf is NaN, not the +0 a skip assumes); no bias of -0
+    for (int l = 0; l < nl; ++l) {
+        for (float w : Kin[l]) if (!std::isfinite(w)) return false;
+        for (float b : Bin[l]) if (!std::isfinite(b) || (b == 0.0f && std::signbit(b))) return false;
+    }
+    std::vector<std::vector<float>> K(Kin), B(Bin);
+    apply_scales(e, K, B);
+    K[0] = Kin[0];  // as pack_fp32_16: layer 0 unscaled, its chain scaled on the way out
+    pack.assign(pk_floats(nh), 0.0f);
+    pack[pk_final(nh) + 33] = std::ldexp(1.0f, -e[0]);
+    for (int kk = 0; kk < in0; ++kk)
+        for (int row = 0; row < 32; ++row) pack[PK_L0W + kk * 32 + row] = K[0][(size_t)kk * 32 + row];
+    for (int row = 0; row < 32; ++row) pack[PK_L0B + row] = B[0][row];
+    for (int j = 0; j < nh; ++j) {
+        const int base = PK_HID + j * PK_HID_STRIDE;
+        for (int k = 0; k < 32; ++k)
+            for (int row = 0; row < 32; ++row) pack[base + ((k >> 2) * 32 + row) * 4 + (k & 3)] = K[j + 1][(size_t)k * 32 + row];
+        for (int row = 0; row < 32; ++row) pack[base + 1024 + row] = B[j + 1][row];
+    }
+    const int fo = pk_final(nh);
+    for (int u = 0; u < 32; ++u) pack[fo + u] = K[nl - 1][u];
+    pack[fo + 32] = B[nl - 1][0];
+    return true;
+}
+
 // ---- the pruned fp32 pack (nr_internal.h PruneInfo; nr_mlp16.h mlp16_fp32_pruned) ----
 //
 // How often each unit of each ReLU layer fires (pre-activation > 0) over PRUNE_POINTS points drawn

@@ -288,7 +288,8 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
     // PRN: the MLP on the pruned fp32 pack (nr_mlp16.h mlp16_fp32_pruned), staged in LDS instead of the
     // full one, which the redo and the out-of-bound form read from global memory
     constexpr bool PRN = RREG;
-    Smem16 S = stage16<PREC, true>(M, PRN ? M.pkp : nullptr);  // (its __syncthreads also covers sf and the fp32x3 copy)
+    // (M.pku: the unit pack instead, for nr_mlp16.h mlp64_fp32_units)
+    Smem16 S = stage16<PREC, true>(M, PRN ? (M.pku ? M.pku : M.pkp) : nullptr);  // (its __syncthreads also covers sf and the fp32x3 copy)
     // converged rays per wave: {p.xyz, pixel} and the frame (the direction is regenerated from
     // the pixel for facingColor; matCapColor does not read it): 21 instead of 42 KB per CU,
     // so that 4 fp32 workgroups share a CU
@@ -350,7 +351,10 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
     // are at most its share of the launch's < 2^32 queue positions; its ray-steps can exceed that
     // (x max_steps), so they are flushed to the launch's counter past 2^30
     uint32_t nsteps = 0, nhit = 0, nconv = 0;
-    uint32_t nredo = 0;  // PRN: wave evaluations redone on the full pack (wave-uniform)
+    // PRN: wave evaluations redone on the full pack (wave-uniform); while M.pku is set -- no redo then --
+    // the wave evaluations of the unit form instead (one scalar register for both), and nuskip the
+    // unit instructions they skipped
+    uint32_t nredo = 0, nuskip = 0;
     uint32_t wit = 0, wit_tail = 0;  // wave iterations, those after the queue drained (stamps)
     // stamps: cycles in refill, shading, MLP, scene, step; and within refill: queue reservation,
     // bulk ray generation, dealing from the ring
@@ -375,7 +379,10 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
         rb_n = (uint32_t)__builtin_amdgcn_readfirstlane((int)rb_n);
         rb_head = (uint32_t)__builtin_amdgcn_readfirstlane((int)rb_head);
         if constexpr (EG) nfq = __builtin_amdgcn_readfirstlane(nfq);
-        if constexpr (PRN) nredo = (uint32_t)__builtin_amdgcn_readfirstlane((int)nredo);
+        if constexpr (PRN) {
+            nredo = (uint32_t)__builtin_amdgcn_readfirstlane((int)nredo);
+            nuskip = (uint32_t)__builtin_amdgcn_readfirstlane((int)nuskip);
+        }
         NR_PHASE(refill);
         // ---- refill free slots from the pixel queue
         if (!qempty || (RING && rb_n > 0)) {
@@ -740,9 +747,14 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
             if constexpr (NX3) asm volatile("" : "+s"(zoff_x3));
             float sdf;
             if constexpr (PRN) {
-                uint32_t redo;
-                sdf = mlp16_fp32_pruned(fresh_kargs()->M, S.s32, fr_of(sfr), pq.x, pq.y, pq.z, smask, redo);
-                nredo += redo;
+                if (fresh_kargs()->M.pku) {
+                    // (the pass's lanes: 4 samples of each of its nb rays)
+                    sdf = mlp64_fp32_units(fresh_kargs()->M, S.s32, fr_of(sfr), pq.x, pq.y, pq.z, ~0ull >> (64 - 4 * nb), nuskip, nredo);
+                } else {
+                    uint32_t redo;
+                    sdf = mlp16_fp32_pruned(fresh_kargs()->M, S.s32, fr_of(sfr), pq.x, pq.y, pq.z, smask, redo);
+                    nredo += redo;
+                }
             } else {
                 sdf = NX3 ? mlp16_x3_normal<(EG ? NR_X3N_ONE_EG : NR_X3N_ONE) != 0>(M, S.s32, (X3L ? x3l : M.x3lp) + zoff_x3, (X3L ? x3f : M.x3fl) + zoff_x3, fr_of(sfr), pq.x, pq.y,
                                                         pq.z, smask)
@@ -903,9 +915,13 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
         if (MLP_PRIO) set_priority(MLP_PRIO);
         float sdf;
         if constexpr (PRN) {
-            uint32_t redo;
-            sdf = mlp16_fp32_pruned(fresh_kargs()->M, S.s32, fr_of(rf), p.x, p.y, p.z, tmask, redo);
-            nredo += redo;
+            if (fresh_kargs()->M.pku) {
+                sdf = mlp64_fp32_units(fresh_kargs()->M, S.s32, fr_of(rf), p.x, p.y, p.z, lm, nuskip, nredo);
+            } else {
+                uint32_t redo;
+                sdf = mlp16_fp32_pruned(fresh_kargs()->M, S.s32, fr_of(rf), p.x, p.y, p.z, tmask, redo);
+                nredo += redo;
+            }
         } else {
             sdf = mlp16(M, S.s32, S.slp, S.sfl, prec, fr_of(rf), p.x, p.y, p.z, tmask, M.lp_clamp != 0);
         }
@@ -1029,7 +1045,8 @@ __global__ __launch_bounds__(EG && EGL ? 64 * NR_EG_WAVES : 256, EG ? NR_TRACE_B
         if (maxit) atomicMax(T.stats + 2, (unsigned long long)maxit);
         if (EG && nfine) atomicAdd(T.stats + 4, (unsigned long long)nfine);
         if (EG && nswitch) atomicAdd(T.stats + 5, (unsigned long long)nswitch);
-        if (PRN && nredo) atomicAdd(T.stats + 6, (unsigned long long)nredo);
+        if (PRN && nredo) atomicAdd(T.stats + (M.pku ? 8 : 6), (unsigned long long)nredo);
+        if (PRN && nuskip) atomicAdd(T.stats + 7, (unsigned long long)nuskip);
     }
 }
 

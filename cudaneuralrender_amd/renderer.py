@@ -126,6 +126,25 @@ def pack_x3(dims, kernels, biases):
     return a, f, ok.value
 
 
+def pack_fp32_units(dims, kernels, biases):
+    """The unit pack of a fused-shape network (nr_pack_fp32_units; host only) as float32, or None
+    when it is refused (layout: csrc/nr_internal.h pack_fp32_units)."""
+    L = lib()
+    nl = len(kernels)
+    d = (ctypes.c_int * (nl + 1))(*dims)
+    ks_ = [np.ascontiguousarray(k, np.float32) for k in kernels]
+    bs = [np.ascontiguousarray(b, np.float32) for b in biases]
+    kp = (_FP * nl)(*[_fptr(k) for k in ks_])
+    bp = (_FP * nl)(*[_fptr(b) for b in bs])
+    n, hp = ctypes.c_long(0), ctypes.c_int(0)
+    check(L.nr_pack_fp32_units(nl, d, kp, bp, None, 0, ctypes.byref(n), ctypes.byref(hp)))
+    if not hp.value:
+        return None
+    pack = np.zeros(n.value, np.float32)
+    check(L.nr_pack_fp32_units(nl, d, kp, bp, _fptr(pack), n.value, ctypes.byref(n), ctypes.byref(hp)))
+    return pack
+
+
 def pack_fp32_pruned(dims, kernels, biases, mode=1):
     """The library's fp32 packs of a fused-shape network (nr_pack_fp32_pruned; host only): a dict
     with full (float32), clamp, and -- None / empty when the scaled pack is refused -- pruned
@@ -343,6 +362,20 @@ class Renderer:
         cand, ks, order = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32), np.zeros((n.value, 32), np.int32)
         self._chk(self._L.nr_prune_info(self._ctx, ctypes.byref(n), _iptr(cand), _iptr(ks), _iptr(order), n.value))
         return {"cand": cand, "ks": ks, "order": order}
+
+    def set_unit_skip(self, on):
+        """nr_set_unit_skip: the batched fp32 tracer's one-instruction-per-unit form, which skips
+        the units that are +0 at every point of a wave (default on; it runs while the prune mode
+        is 1).  Same images and statistics either way."""
+        self._chk(self._L.nr_set_unit_skip(self._ctx, int(bool(on))))
+        return self
+
+    def unit_skip_counts(self):
+        """nr_unit_skip_counts: (issued, skipped) of the last render_batch -- the unit instructions
+        its waves came to, and those of them that were not executed."""
+        a, b = ctypes.c_ulonglong(0), ctypes.c_ulonglong(0)
+        self._chk(self._L.nr_unit_skip_counts(self._ctx, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
 
     def prune_redos(self):
         """nr_prune_redos: wave evaluations the last render_batch redid on the full fp32 pack."""

@@ -689,6 +689,23 @@ int nr_set_endgame(nr_ctx *ctx, float tau);
 int nr_set_prune(nr_ctx *ctx, int mode);
 int nr_prune_info(const nr_ctx *ctx, int *nrelu, int *cand, int *ks, int *order, int cap_layers);
 int nr_prune_redos(nr_ctx *ctx, unsigned long long *redos);
+
+/* The batched fp32 tracer (nr_render_batch), one matrix instruction per hidden unit (added after
+ * 3.0; NR_ABI_VERSION stays 3): a unit whose activation is +0 at every point a wave holds is not
+ * issued -- the images and statistics are the same bit for bit.  on (the default): this form runs
+ * while the prune mode is 1; nr_set_prune 0 and 2, and on = 0, run the paths they ran before.
+ * Networks whose scaled pack is refused, or with a non-finite weight or a bias of -0, never take
+ * it.  nr_unit_skip_counts, for the last nr_render_batch: *issued = the unit instructions its
+ * waves came to (one per input unit of layer 0 and of every hidden layer, for one wave of 64
+ * points), *skipped = those of them that were not executed, so skipped <= issued and
+ * issued - skipped ran on the matrix core (unit 0 of a hidden layer always does; both 0 when the
+ * form did not run).
+ * nr_pack_fp32_units (host only): the pack that form reads (layout: nr_internal.h), *has_pack = 0
+ * and *len = 0 when it is refused. */
+int nr_set_unit_skip(nr_ctx *ctx, int on);
+int nr_unit_skip_counts(nr_ctx *ctx, unsigned long long *issued, unsigned long long *skipped);
+int nr_pack_fp32_units(int nlayers, const int *dims, const float *const *kernels, const float *const *biases,
+                       float *pack, long cap, long *len, int *has_pack);
 /* Temporal scheduling: each launch (a frame, or a batch's launch of up to 32 frames)
  * records its 8x8 pixel blocks' longest ray (the max over the batch's frames) and the next
  * launch of the same size/shard dispenses blocks longest-first (pixels are unaffected --

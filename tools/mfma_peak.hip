@@ -1,10 +1,17 @@
 // mfma_peak.hip -- sustained rate of back-to-back independent v_mfma_f32_16x16x4_f32 (the
 // fp32 MLP's instruction) and v_mfma_f32_32x32x16_bf16, waves per SIMD 1..4, no VALU work:
 // the practical ceiling the MLP kernels are measured against.  Prints TFLOP/s.
+// Then the unit-skip section: v_mfma_f32_32x32x1_2b_f32 (K = 1, two 32-point blocks) with
+// independent accumulators, as one dependent accumulate chain, with a wave-uniform "is this
+// unit +0 in every live lane" test and branch between instances, and with v_permlane32_swap
+// beside it; every figure as median [min, max] of 7 timed launches, next to the 16x16x4
+// stream timed the same way.  It also checks the instruction's D layout with exact integers.
 // build: hipcc --offload-arch=gfx950 -O3 mfma_peak.hip -o bin/mfma_peak
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
+#include <vector>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -54,6 +61,185 @@ __global__ void k_bf16(float *out, int iters, float a0, float b0) {
     float s = 0;
     for (int i = 0; i < 4; ++i) s += c[i][0] + c[i][15];
     out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
+
+typedef float f32x32 __attribute__((ext_vector_type(32)));
+
+// v_mfma_f32_32x32x1_2b_f32, NACC independent accumulators (NACC = 1: one dependent chain)
+template <int NACC>
+__global__ void k_u(float *out, int iters, float a0, float b0) {
+    f32x32 c[NACC];
+    for (int i = 0; i < NACC; ++i) c[i] = f32x32{};
+    const float a = a0 + threadIdx.x * 1e-9f, b = b0;
+    for (int it = 0; it < iters; ++it)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) c[i % NACC] = __builtin_amdgcn_mfma_f32_32x32x1f32(a, b, c[i % NACC], 0, 0, 0);
+    float s = 0;
+    for (int i = 0; i < NACC; ++i) s += c[i][0] + c[i][31];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
+
+// one dependent chain over 8 "units" per iteration: unit k is issued only if its activation
+// av[k] has a nonzero bit pattern in some live lane.  The empty asm keeps the compiler from
+// hoisting the loop-invariant test out of the loop.  MODE 0: compare, scalar and, scalar branch
+// in front of each instance; 1: the eight compares and ands first (as after a layer's
+// epilogue), then a scalar test and branch per instance; 2: compare and and per instance, no
+// branch (every unit issued): the cost of the test without the branch
+template <int MODE>
+__global__ void k_u_skip(float *out, int iters, float b0, const float *av, unsigned long long live) {
+    f32x32 c = f32x32{};
+    const int lane = threadIdx.x & 63;
+    unsigned a[8];
+    for (int k = 0; k < 8; ++k) a[k] = __float_as_uint(av[k * 64 + lane]);
+    float w = b0 + lane * 1e-9f;
+    asm volatile("" : "+v"(w));
+    unsigned long long any = 0;
+    for (int it = 0; it < iters; ++it) {
+        if constexpr (MODE == 1) {
+            unsigned long long m[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                asm volatile("" : "+v"(a[k]));
+                m[k] = __builtin_amdgcn_ballot_w64(a[k] != 0u) & live;
+                asm volatile("" : "+s"(m[k]));
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (m[k]) c = __builtin_amdgcn_mfma_f32_32x32x1f32(w, __uint_as_float(a[k]), c, 0, 0, 0);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                asm volatile("" : "+v"(a[k]));
+                const unsigned long long m = __builtin_amdgcn_ballot_w64(a[k] != 0u) & live;
+                if constexpr (MODE == 2) {
+                    any |= m;
+                    c = __builtin_amdgcn_mfma_f32_32x32x1f32(w, __uint_as_float(a[k]), c, 0, 0, 0);
+                } else if (m) {
+                    c = __builtin_amdgcn_mfma_f32_32x32x1f32(w, __uint_as_float(a[k]), c, 0, 0, 0);
+                }
+            }
+        }
+    }
+    out[blockIdx.x * blockDim.x + threadIdx.x] = c[0] + c[31] + (float)(unsigned)(any >> 40);
+}
+
+// one dependent chain with NS v_permlane32_swap (independent registers) after every instance
+template <int NS>
+__global__ void k_u_swap(float *out, int iters, float a0, float b0) {
+    f32x32 c = f32x32{};
+    const float a = a0 + threadIdx.x * 1e-9f, b = b0;
+    unsigned v[8];
+    for (int i = 0; i < 8; ++i) v[i] = threadIdx.x * 8u + i;
+    for (int it = 0; it < iters; ++it)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            c = __builtin_amdgcn_mfma_f32_32x32x1f32(a, b, c, 0, 0, 0);
+#pragma unroll
+            for (int q = 0; q < NS; ++q) {
+                const int x = (2 * (i + q)) & 7;
+                auto r = __builtin_amdgcn_permlane32_swap(v[x], v[x + 1], false, false);
+                v[x] = r[0];
+                v[x + 1] = r[1];
+            }
+        }
+    unsigned s = 0;
+    for (int i = 0; i < 8; ++i) s += v[i];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = c[0] + c[31] + (float)s;
+}
+
+// D layout: A = 1 + row + 100 * block in lane 32 * block + row, B = 1 + 3 * column + 1000 * block
+// in lane 32 * block + column (asymmetric, exact in f32); every lane dumps its 32 registers
+__global__ void k_u_layout(float *out) {
+    const int lane = threadIdx.x & 63;
+    const float a = 1.0f + (lane & 31) + 100.0f * (lane >> 5);
+    const float b = 1.0f + 3.0f * (lane & 31) + 1000.0f * (lane >> 5);
+    f32x32 c = __builtin_amdgcn_mfma_f32_32x32x1f32(a, b, f32x32{}, 0, 0, 0);
+    for (int r = 0; r < 32; ++r) out[lane * 32 + r] = c[r];
+}
+
+template <class F>
+static bool timed(const char *name, int wps, double flop, double peak, F launch) {
+    hipEvent_t e0, e1;
+    if (hipEventCreate(&e0) || hipEventCreate(&e1)) return false;
+    launch();
+    if (hipDeviceSynchronize()) return false;
+    std::vector<double> tf;
+    for (int r = 0; r < 7; ++r) {
+        if (hipEventRecord(e0, 0)) return false;
+        launch();
+        if (hipEventRecord(e1, 0) || hipEventSynchronize(e1)) return false;
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, e0, e1)) return false;
+        tf.push_back(flop / (ms * 1e-3) / 1e12);
+    }
+    std::sort(tf.begin(), tf.end());
+    printf("%-58s waves/SIMD %d: %6.1f TF/s [%6.1f, %6.1f]  (%.3f of %.1f)\n", name, wps, tf[3], tf[0], tf[6], tf[3] / peak, peak);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return true;
+}
+
+static int unit_skip_section(int cus, float *out) {
+    printf("# unit skip: v_mfma_f32_32x32x1_2b_f32, median [min, max] of 7 launches; a skipped unit counts as issued FLOP\n");
+    // D layout first: block b = reg / 16, column = lane % 32, row = (reg % 4) + 8 * ((reg % 16) / 4) + 4 * (lane / 32)
+    {
+        std::vector<float> h(64 * 32);
+        hipLaunchKernelGGL(k_u_layout, dim3(1), dim3(64), 0, 0, out);
+        if (hipMemcpy(h.data(), out, h.size() * 4, hipMemcpyDeviceToHost)) return 1;
+        int bad = 0;
+        for (int lane = 0; lane < 64; ++lane)
+            for (int r = 0; r < 32; ++r) {
+                const int blk = r / 16, col = lane % 32, row = (r % 4) + 8 * ((r % 16) / 4) + 4 * (lane / 32);
+                const float want = (1.0f + row + 100.0f * blk) * (1.0f + 3.0f * col + 1000.0f * blk);
+                bad += h[lane * 32 + r] != want;
+            }
+        printf("D layout (block = reg / 16, column = lane %% 32, row = reg %% 4 + 8 * (reg %% 16 / 4) + 4 * (lane / 32)): %d of 2048 wrong\n", bad);
+    }
+    float *av;
+    if (hipMalloc(&av, 3 * 8 * 64 * 4)) return 1;
+    {
+        // pattern 0: every unit nonzero in every lane; 1: units 1, 4, 6 are +0 in all lanes;
+        // 2: the same three units nonzero in lane 63 only, which the live mask leaves out
+        std::vector<float> h(3 * 8 * 64);
+        for (int p = 0; p < 3; ++p)
+            for (int k = 0; k < 8; ++k)
+                for (int l = 0; l < 64; ++l) {
+                    const bool dead = k == 1 || k == 4 || k == 6;
+                    h[(p * 8 + k) * 64 + l] = p == 0 || !dead ? 1e-3f : (p == 2 && l == 63 ? 1e-3f : 0.0f);
+                }
+        if (hipMemcpy(av, h.data(), h.size() * 4, hipMemcpyHostToDevice)) return 1;
+    }
+    const int iters = 2048;
+    for (int wps = 1; wps <= 4; wps += 3) {
+        const int grid = cus * wps;
+        const double f16 = (double)grid * 4 * iters * 2 * 8.0 * 2 * 16 * 16 * 4, fu = (double)grid * 4 * iters * 8.0 * 2 * 32 * 32 * 2;
+        bool ok = true;
+        ok &= timed("16x16x4 f32, 8 independent accumulators", wps, f16, 157.3,
+                    [&] { hipLaunchKernelGGL(k_f32, dim3(grid), dim3(256), 0, 0, out, 2 * iters, 1.0f, 1e-3f); });
+        ok &= timed("32x32x1_2b f32, 2 independent accumulators", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u<2>, dim3(grid), dim3(256), 0, 0, out, iters, 1.0f, 1e-3f); });
+        ok &= timed("32x32x1_2b f32, one dependent chain", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u<1>, dim3(grid), dim3(256), 0, 0, out, iters, 1.0f, 1e-3f); });
+        ok &= timed("chain + test and branch per unit, 8 of 8 issued", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u_skip<0>, dim3(grid), dim3(256), 0, 0, out, iters, 1e-3f, av, ~0ull); });
+        ok &= timed("chain + test and branch per unit, 5 of 8 issued", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u_skip<0>, dim3(grid), dim3(256), 0, 0, out, iters, 1e-3f, av + 512, ~0ull); });
+        ok &= timed("chain + test and branch, 5 of 8, stale lane 63 masked off", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u_skip<0>, dim3(grid), dim3(256), 0, 0, out, iters, 1e-3f, av + 1024, ~0ull >> 1); });
+        ok &= timed("chain, 8 tests first, then branch per unit, 8 of 8 issued", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u_skip<1>, dim3(grid), dim3(256), 0, 0, out, iters, 1e-3f, av, ~0ull); });
+        ok &= timed("chain, 8 tests first, then branch per unit, 5 of 8 issued", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u_skip<1>, dim3(grid), dim3(256), 0, 0, out, iters, 1e-3f, av + 512, ~0ull); });
+        ok &= timed("chain + test per unit, no branch, 8 of 8 issued", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u_skip<2>, dim3(grid), dim3(256), 0, 0, out, iters, 1e-3f, av, ~0ull); });
+        ok &= timed("chain + 1 v_permlane32_swap per instance", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u_swap<1>, dim3(grid), dim3(256), 0, 0, out, iters, 1.0f, 1e-3f); });
+        ok &= timed("chain + 2 v_permlane32_swap per instance", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u_swap<2>, dim3(grid), dim3(256), 0, 0, out, iters, 1.0f, 1e-3f); });
+        if (!ok) return 1;
+    }
+    (void)hipFree(av);
+    return 0;
 }
 
 int main() {
@@ -109,5 +295,5 @@ int main() {
             const double tf = (double)grid * 4 * iters * 8.0 * 2 * 16 * 16 * 4 / (ms * 1e-3) / 1e12;
             printf("16x16x4 f32 + %d v_add_f32 per MFMA, waves/SIMD %d: %.1f TF/s (%.3f of 157.3)\n", nv, wps, tf, tf / 157.3);
         }
-    return 0;
+    return unit_skip_section(cus, out);
 }
