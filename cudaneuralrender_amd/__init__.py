@@ -13,6 +13,8 @@ from ._lib import NR_PROJ_CONVERGED, NR_PROJ_FLAT, NR_PROJ_LIMIT, NRProjectOpts 
 from .renderer import (NR_COLOR_FACING, NR_COLOR_MATCAP, Group, Renderer, assemble_shards, camera,  # noqa: F401
                        load_png, pack_fp32_pruned, pack_fp32_units, pack_x3, read_keras_h5, save_obj, save_png, save_ppm, shard_rows, batch_frames_per_launch,
                        group_layout)
+from ._lib import NR_COMPOSE_MAX_NETS, NR_COMPOSE_MAX_PARTS, NR_PART_OP, NRComposeStats, NRPart  # noqa: F401
+from .renderer import Composition, compose_bound, make_parts  # noqa: F401
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_DIR = os.path.dirname(PKG_DIR)

@@ -45,7 +45,12 @@ EXPORTS = [
     "nr_mlp_gradient", "nr_project_points",
     "nr_pack_fp32_pruned", "nr_set_prune", "nr_prune_info", "nr_prune_redos",
     "nr_set_unit_skip", "nr_unit_skip_counts", "nr_pack_fp32_units",
+    "nr_compose_create", "nr_compose_destroy", "nr_compose_bound", "nr_compose_set_parts", "nr_compose_info",
+    "nr_compose_sample", "nr_compose_trace_rays", "nr_compose_gbuffer", "nr_compose_render",
 ]
+# composed scenes (nr_compose_*): limits and part ops
+NR_COMPOSE_MAX_NETS, NR_COMPOSE_MAX_PARTS = 4, 16
+NR_PART_OP = {"union": 0, "subtract": 1}
 
 
 class NRStats(ctypes.Structure):
@@ -96,6 +101,35 @@ class NRProjectOpts(ctypes.Structure):
         ("max_step", ctypes.c_float),
         ("max_iters", ctypes.c_int),
     ]
+
+
+class NRPart(ctypes.Structure):
+    """nr_part: one placed network of a composition."""
+    _fields_ = [
+        ("net", ctypes.c_int),
+        ("op", ctypes.c_int),
+        ("rot", ctypes.c_float * 9),
+        ("pos", ctypes.c_float * 3),
+        ("scale", ctypes.c_float),
+    ]
+
+
+class NRComposeStats(ctypes.Structure):
+    _fields_ = [
+        ("ray_steps", ctypes.c_uint64),
+        ("shade_evals", ctypes.c_uint64),
+        ("rays_hit", ctypes.c_uint64),
+        ("rays_shaded", ctypes.c_uint64),
+        ("part_evals", ctypes.c_uint64),
+        ("wave_evals", ctypes.c_uint64),
+        ("wave_skips", ctypes.c_uint64),
+        ("iterations", ctypes.c_int32),
+        ("launches", ctypes.c_int32),
+        ("ms_total", ctypes.c_float),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 class NRKernelProf(ctypes.Structure):
@@ -219,6 +253,15 @@ def lib():
         "nr_set_temporal_order": (I, [P, I]),
         "nr_dense_forward": (I, [P, P, P, I, I, I, P, P, L64, I]),
         "nr_debug_stamps": (I, [P, P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+        "nr_compose_create": (I, [P, ctypes.POINTER(P), I, ctypes.POINTER(NRPart), I, ctypes.POINTER(P)]),
+        "nr_compose_destroy": (I, [P]),
+        "nr_compose_bound": (I, [ctypes.POINTER(NRPart), I, I, FP, FP]),
+        "nr_compose_set_parts": (I, [P, ctypes.POINTER(NRPart), I]),
+        "nr_compose_info": (I, [P, IP, IP, FP, FP]),
+        "nr_compose_sample": (I, [P, P, L64, P, P, I, ctypes.POINTER(NRComposeStats)]),
+        "nr_compose_trace_rays": (I, [P, P, P, L64, I, P, P, P, P, P, P, I, ctypes.POINTER(NRComposeStats)]),
+        "nr_compose_gbuffer": (I, [P, I, I, I, P, P, P, P, P, P, I, ctypes.POINTER(NRComposeStats)]),
+        "nr_compose_render": (I, [P, P, I, I, I, P, I, ctypes.POINTER(NRComposeStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -2351,6 +2351,384 @@ int nr_project_points(nr_ctx *c, const float *X, long n, const nr_project_opts *
     return NR_OK;
 }
 
+// ---- composed scenes (nr_compose.hip) ----
+
+struct nr_compose {
+    nr_ctx *owner = nullptr;
+    float *d_packs = nullptr;
+    ComposeArgs A{};              // packs, nets, parts and the bound; the per-call fields are filled per call
+    int npacks = 0;               // distinct packs in d_packs
+    float center[3] = {0, 0, 0}, radius = 0;
+    // the ray cursor on its own 128-byte line + 7 x u64 stats; staging of host rays, points and results;
+    // the frame's geometry buffer (status, normal: 16 B per pixel) and its staging
+    uint32_t *d_cs = nullptr;
+    float *d_io = nullptr;
+    size_t cap_io = 0;
+    float *d_gbuf = nullptr;
+    size_t cap_gbuf = 0;
+    uint32_t *d_out = nullptr;
+    size_t cap_out = 0;
+};
+constexpr size_t COMPOSE_CS_BYTES = 128 + 7 * 8;
+
+int nr_compose_bound(const nr_part *parts, int nparts, int nnets, float center[3], float *radius) {
+    if (!parts) return set_err(nullptr, NR_E_INVALID, "nr_compose: parts is NULL");
+    if (nnets < 1 || nnets > NR_COMPOSE_MAX_NETS) return set_err(nullptr, NR_E_INVALID, "nr_compose: %d nets outside 1..%d", nnets, NR_COMPOSE_MAX_NETS);
+    if (nparts < 1 || nparts > NR_COMPOSE_MAX_PARTS)
+        return set_err(nullptr, NR_E_INVALID, "nr_compose: %d parts outside 1..%d", nparts, NR_COMPOSE_MAX_PARTS);
+    for (int j = 0; j < nparts; ++j) {
+        const nr_part &p = parts[j];
+        if (p.net < 0 || p.net >= nnets) return set_err(nullptr, NR_E_INVALID, "nr_compose: part %d: net %d out of range", j, p.net);
+        if (p.op != NR_PART_UNION && p.op != NR_PART_SUBTRACT) return set_err(nullptr, NR_E_INVALID, "nr_compose: part %d: unknown op %d", j, p.op);
+        if (j == 0 && p.op != NR_PART_UNION) return set_err(nullptr, NR_E_INVALID, "nr_compose: part 0 must be a union");
+        if (!std::isfinite(p.scale) || !(p.scale > 0.0f)) return set_err(nullptr, NR_E_INVALID, "nr_compose: part %d: scale must be finite and > 0", j);
+        if (!std::isfinite(1.0f / p.scale) || !std::isfinite(1.2f * p.scale))
+            return set_err(nullptr, NR_E_INVALID, "nr_compose: part %d: scale out of range", j);
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(p.pos[k])) return set_err(nullptr, NR_E_INVALID, "nr_compose: part %d: non-finite position", j);
+        const float *R = p.rot;
+        double dev = 0.0;
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) {
+                double s = 0.0;
+                for (int k = 0; k < 3; ++k) s += (double)R[3 * a + k] * (double)R[3 * b + k];
+                dev = std::max(dev, std::fabs(s - (a == b ? 1.0 : 0.0)));
+            }
+        const double det = (double)R[0] * ((double)R[4] * R[8] - (double)R[5] * R[7]) -
+                           (double)R[1] * ((double)R[3] * R[8] - (double)R[5] * R[6]) +
+                           (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
+        if (!(dev <= 1e-4) || !(det >= 0.0)) return set_err(nullptr, NR_E_INVALID, "nr_compose: part %d: rot is not a rotation", j);
+    }
+    // the bound: the mean position, and the farthest reach of a part's sphere of radius 1.2 scale
+    float c[3];
+    for (int k = 0; k < 3; ++k) {
+        double s = 0.0;
+        for (int j = 0; j < nparts; ++j) s += (double)parts[j].pos[k];
+        c[k] = (float)(s / (double)nparts);
+    }
+    double rd = 0.0;
+    for (int j = 0; j < nparts; ++j) {
+        double q = 0.0;
+        for (int k = 0; k < 3; ++k) {
+            const double t = (double)parts[j].pos[k] - (double)c[k];
+            q += t * t;
+        }
+        rd = std::max(rd, std::sqrt(q) * (1.0 + 0x1p-20) + (double)(1.2f * parts[j].scale));
+    }
+    float r = (float)rd;
+    if ((double)r < rd) r = std::nextafterf(r, INFINITY);
+    if (!std::isfinite(r) || !std::isfinite(r * r)) return set_err(nullptr, NR_E_INVALID, "nr_compose: the bound is not finite");
+    if (center) for (int k = 0; k < 3; ++k) center[k] = c[k];
+    if (radius) *radius = r;
+    return NR_OK;
+}
+
+// the parts and their bound into the composition (validated first: nothing changes on an error)
+static int compose_set(nr_compose *cp, const nr_part *parts, int nparts) {
+    float c[3], r;
+    const int rc = nr_compose_bound(parts, nparts, cp->A.nnets, c, &r);
+    if (rc != NR_OK) { cp->owner->err = nr_last_error(nullptr); return rc; }
+    ComposeArgs &A = cp->A;
+    A.nparts = nparts;
+    for (int j = 0; j < nparts; ++j) {
+        ComposePart &P = A.parts[j];
+        memcpy(P.rot, parts[j].rot, sizeof P.rot);
+        memcpy(P.pos, parts[j].pos, sizeof P.pos);
+        P.scale = parts[j].scale;
+        P.inv_s = 1.0f / parts[j].scale;
+        P.net = parts[j].net;
+        P.op = parts[j].op;
+    }
+    for (int k = 0; k < 3; ++k) { cp->center[k] = c[k]; A.center[k] = c[k]; }
+    cp->radius = r;
+    A.r2 = r * r;
+    return NR_OK;
+}
+
+int nr_compose_create(nr_ctx *owner, nr_ctx *const *nets, int nnets, const nr_part *parts, int nparts, nr_compose **out) {
+    if (out) *out = nullptr;
+    if (!owner || !nets || !parts || !out) return set_err(owner, NR_E_INVALID, "nr_compose_create: NULL argument");
+    if (nnets < 1 || nnets > NR_COMPOSE_MAX_NETS)
+        return set_err(owner, NR_E_INVALID, "nr_compose_create: %d nets outside 1..%d", nnets, NR_COMPOSE_MAX_NETS);
+    int rc;
+    if ((rc = nr_compose_bound(parts, nparts, nnets, nullptr, nullptr)) != NR_OK) { owner->err = nr_last_error(nullptr); return rc; }
+    size_t total = 0;
+    int npacks = 0;
+    ComposeNet cn[NR_COMPOSE_MAX_NETS];
+    for (int i = 0; i < nnets; ++i) {
+        const nr_ctx *s = nets[i];
+        if (!s) return set_err(owner, NR_E_INVALID, "nr_compose_create: net %d is NULL", i);
+        if (s->dims.empty()) return set_err(owner, NR_E_STATE, "nr_compose_create: net %d has no network", i);
+        if (!s->fused || !s->d_pack16)
+            return set_err(owner, NR_E_FORMAT, "nr_compose_create: net %d is not a [3|4, 32, ..., 32, 1] network (no fp32 pack)", i);
+        if (s->device != owner->device) return set_err(owner, NR_E_INVALID, "nr_compose_create: net %d lives on device %d, the owner on %d", i, s->device, owner->device);
+        int same = -1;
+        for (int k = 0; k < i && same < 0; ++k)
+            if (nets[k] == nets[i]) same = k;
+        cn[i].off = same >= 0 ? cn[same].off : (int)(total / 4);
+        cn[i].in0 = s->mlp16.in0;
+        cn[i].nh = s->mlp16.nh;
+        cn[i].f32_clamp = s->mlp16.f32_clamp;
+        if (same < 0) { total += (size_t)s->mlp16.pk_bytes; ++npacks; }
+    }
+    // every workgroup shape the launches use must fit a CU's LDS: the packs and four waves' lists
+    // at the least, twelve waves' for more than one pack (compose_threads)
+    ComposeArgs probe{};
+    probe.pack_bytes = (int)total;
+    const int threads = npacks > 1 ? 768 : 256;
+    if (total > (size_t)NR_LDS_PER_CU || compose_lds_bytes(probe, threads) > NR_LDS_PER_CU)
+        return set_err(owner, NR_E_INVALID, "nr_compose_create: the packs need %zu bytes of LDS (limit %d with the per-wave lists)", total, NR_LDS_PER_CU);
+    nr_compose *cp = new (std::nothrow) nr_compose();
+    if (!cp) return set_err(owner, NR_E_NOMEM, "out of host memory");
+    cp->owner = owner;
+    cp->npacks = npacks;
+    cp->A.nnets = nnets;
+    cp->A.pack_bytes = (int)total;
+    for (int i = 0; i < nnets; ++i) cp->A.nets[i] = cn[i];
+    if ((rc = compose_set(cp, parts, nparts)) != NR_OK) { delete cp; return rc; }
+    hipError_t e = hipSetDevice(owner->device);
+    if (e == hipSuccess) e = hipMalloc(&cp->d_packs, total);
+    if (e == hipSuccess) e = hipMalloc(&cp->d_cs, COMPOSE_CS_BYTES);
+    for (int i = 0; i < nnets && e == hipSuccess; ++i) {
+        // (a blocking copy: the source may be destroyed as soon as this returns)
+        bool first = true;
+        for (int k = 0; k < i; ++k) first = first && nets[k] != nets[i];
+        if (first) e = hipMemcpy(cp->d_packs + cn[i].off, nets[i]->d_pack16, (size_t)nets[i]->mlp16.pk_bytes, hipMemcpyDeviceToDevice);
+    }
+    if (e != hipSuccess) {
+        dfree(cp->d_packs); dfree(cp->d_cs);
+        delete cp;
+        return set_err(owner, NR_E_HIP, "nr_compose_create: %s", hipGetErrorString(e));
+    }
+    cp->A.packs = cp->d_packs;
+    *out = cp;
+    return NR_OK;
+}
+
+int nr_compose_destroy(nr_compose *cp) {
+    if (!cp) return NR_OK;
+    nr_ctx *c = cp->owner;
+    (void)hipSetDevice(c->device);
+    if (!(c->use_own && !c->own_stream)) (void)hipStreamSynchronize(c->stream);
+    dfree(cp->d_packs); dfree(cp->d_cs); dfree(cp->d_io); dfree(cp->d_gbuf); dfree(cp->d_out);
+    delete cp;
+    return NR_OK;
+}
+
+int nr_compose_set_parts(nr_compose *cp, const nr_part *parts, int nparts) {
+    if (!cp) return set_err(nullptr, NR_E_INVALID, "nr_compose_set_parts: composition is NULL");
+    return compose_set(cp, parts, nparts);
+}
+
+int nr_compose_info(const nr_compose *cp, int *nnets, int *nparts, float center[3], float *radius) {
+    if (!cp) return set_err(nullptr, NR_E_INVALID, "nr_compose_info: composition is NULL");
+    if (nnets) *nnets = cp->A.nnets;
+    if (nparts) *nparts = cp->A.nparts;
+    if (center) for (int k = 0; k < 3; ++k) center[k] = cp->center[k];
+    if (radius) *radius = cp->radius;
+    return NR_OK;
+}
+
+// The workgroup of a k_compose launch and the grid: one pack keeps k_query's shape (4 waves, two
+// workgroups per CU by default, as query_grid); more packs leave room for one or two workgroups
+// per CU, so one of 12 waves holds three waves per SIMD.  nr_set_occupancy on the owner asks for
+// that many 4-wave workgroups per CU instead, as far as the LDS allows.
+static void compose_shape(const nr_compose *cp, size_t n, int &threads, int &grid) {
+    const nr_ctx *c = cp->owner;
+    const bool one = cp->npacks == 1;
+    int bpc;
+    if (c->blocks_per_cu > 0 || one) {
+        threads = 256;
+        const int fit = std::max(1, NR_LDS_PER_CU / compose_lds_bytes(cp->A, threads));
+        bpc = std::min(c->blocks_per_cu > 0 ? c->blocks_per_cu : 2, fit);
+    } else {
+        threads = 768;
+        bpc = 1;
+    }
+    grid = (int)std::max<size_t>(1, std::min<size_t>((n + threads - 1) / threads, (size_t)num_cus(c->device) * bpc));
+}
+
+static void compose_stats(const unsigned long long *hs, bool normals, int launches, float ms, nr_compose_stats *stats) {
+    nr_compose_stats st{};
+    st.ray_steps = hs[0];
+    st.rays_hit = hs[1];
+    st.iterations = (int32_t)hs[2];
+    st.rays_shaded = hs[3];
+    st.shade_evals = normals ? 4ull * hs[3] : 0ull;
+    st.part_evals = hs[4];
+    st.wave_evals = hs[5];
+    st.wave_skips = hs[6];
+    st.launches = launches;
+    st.ms_total = ms;
+    *stats = st;
+}
+
+// n caller-supplied rays, or with origins == NULL the W x H pixel rays of the owner's view, through
+// one k_compose launch; with `out` the colouring launch follows (nr_compose_render: status and normal
+// then live in the composition's geometry buffer).
+static int compose_rays(nr_compose *cp, const char *fn, const float *origins, const float *dirs, long n, int W, int H,
+                        int max_steps, int32_t *status, int32_t *steps, float *t, float *position, float *normal,
+                        int32_t *part, uint32_t *out, int loc, nr_compose_stats *stats) {
+    nr_ctx *c = cp->owner;
+    if (n == 0) { if (stats) *stats = nr_compose_stats{}; return NR_OK; }
+    if (out && c->color_type == NR_COLOR_MATCAP && !c->d_matcap) return set_err(c, NR_E_STATE, "%s: matcap colouring without a matcap", fn);
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    ComposeArgs Q = cp->A;
+    Q.n = n; Q.W = W; Q.H = H;
+    Q.inv_w = 1.0 / (double)W;
+    Q.rcp_w = pow2_rcp(W); Q.rcp_h = pow2_rcp(H);
+    memcpy(Q.inv_view, c->inv_view, sizeof Q.inv_view);
+    Q.max_steps = max_steps; Q.frame = c->frame;
+    Q.cursor = cp->d_cs;
+    Q.stats = reinterpret_cast<unsigned long long *>(cp->d_cs + 32);
+    Q.origins = origins; Q.dirs = dirs;
+    Q.status = status; Q.steps = steps; Q.t = t; Q.position = position; Q.normal = normal; Q.part = part;
+    const size_t N = (size_t)n;
+    const bool host = loc != NR_DEVICE;
+    int rc;
+    if (host) {
+        // staging, in floats: the rays, then every output the caller asked for
+        const size_t need = (origins ? 6 * N : 0) + (status ? N : 0) + (steps ? N : 0) + (t ? N : 0) +
+                            (position ? 3 * N : 0) + (normal ? 3 * N : 0) + (part ? N : 0);
+        if ((rc = ensure_buf(c, cp->d_io, cp->cap_io, need)) != NR_OK) return rc;
+        float *q = cp->d_io;
+        if (origins) {
+            HIPCHK(c, hipMemcpyAsync(q, origins, 3 * N * 4, hipMemcpyHostToDevice, s));
+            HIPCHK(c, hipMemcpyAsync(q + 3 * N, dirs, 3 * N * 4, hipMemcpyHostToDevice, s));
+            Q.origins = q; Q.dirs = q + 3 * N;
+            q += 6 * N;
+        }
+        if (status) { Q.status = reinterpret_cast<int32_t *>(q); q += N; }
+        if (steps) { Q.steps = reinterpret_cast<int32_t *>(q); q += N; }
+        if (t) { Q.t = q; q += N; }
+        if (position) { Q.position = q; q += 3 * N; }
+        if (normal) { Q.normal = q; q += 3 * N; }
+        if (part) { Q.part = reinterpret_cast<int32_t *>(q); q += N; }
+    }
+    uint32_t *dout = out;
+    if (out) {
+        if ((rc = ensure_buf(c, cp->d_gbuf, cp->cap_gbuf, 4 * N)) != NR_OK) return rc;
+        Q.status = reinterpret_cast<int32_t *>(cp->d_gbuf);
+        Q.normal = cp->d_gbuf + N;
+        if (host) {
+            if ((rc = ensure_buf(c, cp->d_out, cp->cap_out, N)) != NR_OK) return rc;
+            dout = cp->d_out;
+        }
+    }
+    int threads, grid;
+    compose_shape(cp, N, threads, grid);
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, hipMemsetAsync(cp->d_cs, 0, COMPOSE_CS_BYTES, s));
+    HIPCHK(c, launch_compose(Q, grid, threads, s));
+    int launches = 2;
+    if (out) {
+        RenderArgs A = render_args(c, W, H, H, H, 1, 0, max_steps);
+        A.out = dout;
+        A.frame = c->frame;
+        memcpy(A.inv_view, c->inv_view, sizeof A.inv_view);
+        memcpy(A.normal, c->normal, sizeof A.normal);
+        HIPCHK(c, launch_compose_color(A, Q.status, Q.normal, s));
+        launches += 1;
+    }
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (host) {
+        if (status) HIPCHK(c, hipMemcpyAsync(status, Q.status, N * 4, hipMemcpyDeviceToHost, s));
+        if (steps) HIPCHK(c, hipMemcpyAsync(steps, Q.steps, N * 4, hipMemcpyDeviceToHost, s));
+        if (t) HIPCHK(c, hipMemcpyAsync(t, Q.t, N * 4, hipMemcpyDeviceToHost, s));
+        if (position) HIPCHK(c, hipMemcpyAsync(position, Q.position, 3 * N * 4, hipMemcpyDeviceToHost, s));
+        if (normal) HIPCHK(c, hipMemcpyAsync(normal, Q.normal, 3 * N * 4, hipMemcpyDeviceToHost, s));
+        if (part) HIPCHK(c, hipMemcpyAsync(part, Q.part, N * 4, hipMemcpyDeviceToHost, s));
+        if (out) HIPCHK(c, hipMemcpyAsync(out, dout, N * 4, hipMemcpyDeviceToHost, s));
+    }
+    unsigned long long hs[7];
+    if (stats) HIPCHK(c, hipMemcpyAsync(hs, Q.stats, sizeof hs, hipMemcpyDeviceToHost, s));
+    float ms = 0.0f;
+    rc = end_timed(c, stats != nullptr, loc, s, &ms);
+    if (rc != NR_OK || !stats) return rc;
+    compose_stats(hs, Q.normal != nullptr, launches, ms, stats);
+    return NR_OK;
+}
+
+int nr_compose_trace_rays(nr_compose *cp, const float *origins, const float *dirs, long n, int max_steps, int32_t *status,
+                          int32_t *steps, float *t, float *position, float *normal, int32_t *part, int loc,
+                          nr_compose_stats *stats) {
+    if (!cp) return set_err(nullptr, NR_E_INVALID, "nr_compose_trace_rays: composition is NULL");
+    nr_ctx *c = cp->owner;
+    if (n < 0 || n > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_compose_trace_rays: n = %ld outside [0, 2^30]", n);
+    if (max_steps < 1) return set_err(c, NR_E_INVALID, "nr_compose_trace_rays: max_steps < 1");
+    if (n > 0 && (!origins || !dirs)) return set_err(c, NR_E_INVALID, "nr_compose_trace_rays: NULL rays");
+    return compose_rays(cp, "nr_compose_trace_rays", origins, dirs, n, 1, 1, max_steps, status, steps, t, position, normal,
+                        part, nullptr, loc, stats);
+}
+
+int nr_compose_gbuffer(nr_compose *cp, int W, int H, int max_steps, int32_t *status, int32_t *steps, float *t, float *position,
+                       float *normal, int32_t *part, int loc, nr_compose_stats *stats) {
+    if (!cp) return set_err(nullptr, NR_E_INVALID, "nr_compose_gbuffer: composition is NULL");
+    nr_ctx *c = cp->owner;
+    if (W < 1 || H < 1 || (long)W * H > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_compose_gbuffer: bad size %dx%d", W, H);
+    if (max_steps < 1) return set_err(c, NR_E_INVALID, "nr_compose_gbuffer: max_steps < 1");
+    return compose_rays(cp, "nr_compose_gbuffer", nullptr, nullptr, (long)W * H, W, H, max_steps, status, steps, t, position,
+                        normal, part, nullptr, loc, stats);
+}
+
+int nr_compose_render(nr_compose *cp, uint32_t *out, int W, int H, int max_steps, int32_t *part, int loc,
+                      nr_compose_stats *stats) {
+    if (!cp) return set_err(nullptr, NR_E_INVALID, "nr_compose_render: composition is NULL");
+    nr_ctx *c = cp->owner;
+    if (!out) return set_err(c, NR_E_INVALID, "nr_compose_render: out is NULL");
+    if (W < 1 || H < 1 || (long)W * H > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_compose_render: bad size %dx%d", W, H);
+    if (max_steps < 1) return set_err(c, NR_E_INVALID, "nr_compose_render: max_steps < 1");
+    return compose_rays(cp, "nr_compose_render", nullptr, nullptr, (long)W * H, W, H, max_steps, nullptr, nullptr, nullptr,
+                        nullptr, nullptr, part, out, loc, stats);
+}
+
+int nr_compose_sample(nr_compose *cp, const float *points, long n, float *value, int32_t *owner, int loc,
+                      nr_compose_stats *stats) {
+    if (!cp) return set_err(nullptr, NR_E_INVALID, "nr_compose_sample: composition is NULL");
+    nr_ctx *c = cp->owner;
+    if (n < 0 || n > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_compose_sample: n = %ld outside [0, 2^30]", n);
+    if (n > 0 && !points) return set_err(c, NR_E_INVALID, "nr_compose_sample: points is NULL");
+    if (n == 0) { if (stats) *stats = nr_compose_stats{}; return NR_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    ComposeArgs Q = cp->A;
+    Q.n = n; Q.frame = c->frame;
+    Q.points = points; Q.value = value; Q.owner = owner;
+    Q.stats = reinterpret_cast<unsigned long long *>(cp->d_cs + 32);
+    const size_t N = (size_t)n;
+    const bool host = loc != NR_DEVICE;
+    if (host) {
+        int rc;
+        if ((rc = ensure_buf(c, cp->d_io, cp->cap_io, 3 * N + (value ? N : 0) + (owner ? N : 0))) != NR_OK) return rc;
+        float *q = cp->d_io;
+        HIPCHK(c, hipMemcpyAsync(q, points, 3 * N * 4, hipMemcpyHostToDevice, s));
+        Q.points = q; q += 3 * N;
+        if (value) { Q.value = q; q += N; }
+        if (owner) { Q.owner = reinterpret_cast<int32_t *>(q); q += N; }
+    }
+    // 4-wave workgroups, as many per CU as the packs allow (at most k_query's three)
+    const int fit = std::max(1, std::min(3, NR_LDS_PER_CU / std::max(1, Q.pack_bytes)));
+    const int bpc = c->blocks_per_cu > 0 ? std::min(c->blocks_per_cu, fit) : fit;
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + 255) / 256, (size_t)num_cus(c->device) * bpc));
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, hipMemsetAsync(cp->d_cs, 0, COMPOSE_CS_BYTES, s));
+    HIPCHK(c, launch_compose_sample(Q, grid, s));
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (host) {
+        if (value) HIPCHK(c, hipMemcpyAsync(value, Q.value, N * 4, hipMemcpyDeviceToHost, s));
+        if (owner) HIPCHK(c, hipMemcpyAsync(owner, Q.owner, N * 4, hipMemcpyDeviceToHost, s));
+    }
+    unsigned long long hs[7];
+    if (stats) HIPCHK(c, hipMemcpyAsync(hs, Q.stats, sizeof hs, hipMemcpyDeviceToHost, s));
+    float ms = 0.0f;
+    const int rc = end_timed(c, stats != nullptr, loc, s, &ms);
+    if (rc != NR_OK || !stats) return rc;
+    hs[0] = (unsigned long long)N;  // points evaluated
+    compose_stats(hs, false, 2, ms, stats);
+    return NR_OK;
+}
+
 int nr_layer_forward(nr_ctx *c, int layer, const float *A, float *Z, long n, int loc) {
     if (!c || n < 0 || (n > 0 && (!A || !Z))) return set_err(c, NR_E_INVALID, "nr_layer_forward: bad arguments");
     int nl = c->dims.empty() ? 0 : (int)c->dims.size() - 1;

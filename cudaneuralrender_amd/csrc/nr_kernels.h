@@ -282,6 +282,53 @@ struct ProjArgs {
     unsigned long long *stats;    // [0] evaluations, [1] converged points, [2] the largest evaluation count
 };
 
+// Composed scenes (nr_compose.hip; nr_compose_*): the distinct fp32 packs back to back in one device
+// buffer (staged into dynamic LDS in that order), the parts, and the queried rays or points.  The
+// struct travels in the kernarg segment: the part loop is wave-uniform and reads it with scalar loads.
+struct ComposeNet {
+    int off;                      // the pack's first float in the buffer (and in LDS)
+    int in0, nh, f32_clamp;       // as MlpArgs
+};
+struct ComposePart {
+    float rot[9];                 // nr_part::rot
+    float pos[3];
+    float scale, inv_s;           // inv_s = 1.0f / scale, formed on the host
+    int net, op;
+};
+constexpr int NR_COMPOSE_NETS = 4, NR_COMPOSE_PARTS = 16;
+struct ComposeArgs {
+    const float *packs;
+    int pack_bytes;               // all packs, a multiple of 16
+    int nnets, nparts;
+    ComposeNet nets[NR_COMPOSE_NETS];
+    ComposePart parts[NR_COMPOSE_PARTS];
+    float center[3], r2;          // the world bound: centre, radius * radius
+    // the rays (QueryArgs' fields; origins NULL: the pixel rays of the W x H view)
+    const float *origins, *dirs;
+    long n;                       // rays or sample points, <= 2^30
+    int W, H;
+    double inv_w;
+    float rcp_w, rcp_h;
+    float inv_view[12];
+    int max_steps, frame;
+    int32_t *status, *steps;
+    float *t, *position, *normal;
+    int32_t *part;                // [n] the owner of a hit, -1 otherwise
+    // k_compose_sample
+    const float *points;          // [n][3]
+    float *value;                 // [n]
+    int32_t *owner;               // [n]
+    uint32_t *cursor;             // next ray to deal (zeroed before the launch)
+    unsigned long long *stats;    // [0] ray-steps, [1] rays that entered the bound, [2] max steps, [3] hits,
+                                  // [4] in-bound (marching ray, part) pairs, [5] wave evaluations issued, [6] skipped
+};
+// dynamic LDS of a k_compose workgroup of `threads` threads: the packs, then one list of converged rays per wave
+int compose_lds_bytes(const ComposeArgs &C, int threads);
+hipError_t launch_compose(const ComposeArgs &C, int grid, int threads, hipStream_t st);         // threads: 256, 512 or 768
+hipError_t launch_compose_sample(const ComposeArgs &C, int grid, hipStream_t st);               // 4-wave workgroups
+// colours the HIT pixels of a W x H geometry buffer (A: W, H, out, view, colouring), 0 elsewhere
+hipError_t launch_compose_color(const RenderArgs &A, const int32_t *status, const float *normal, hipStream_t st);
+
 int dense_lds_bytes(int in, int out);
 int grad_lds_bytes(const MlpArgs &M, const GradArgs &G);  // one k_grad workgroup's dynamic LDS
 hipError_t launch_grad(const GradArgs &G, const MlpArgs &M, int grid, hipStream_t st);  // 4-wave workgroups

@@ -12,6 +12,7 @@ import numpy as np
 from ._lib import (NR_AA_CONTRAST_DEFAULT, NR_AA_MODE, NR_COLOR_FACING, NR_COLOR_MATCAP, NR_DEVICE, NR_GROUP_ASYNC,
                    NR_GROUP_COPY, NR_HOST, NR_PRECISION, NR_SCENE, NR_SCHEDULE, NRFrame, NRKernelProf, NRLight, NRProjectOpts,
                    NRStats, check, lib)
+from ._lib import NR_PART_OP, NRComposeStats, NRPart
 
 _FP = ctypes.POINTER(ctypes.c_float)
 
@@ -867,3 +868,155 @@ class Group:
         check(self._L.nr_group_render_batch(self._g, fr, len(cams), W, H, band, max_steps, NR_DEVICE,
                                             ctypes.byref(st) if with_stats else None))
         return st.as_dict() if with_stats else None
+
+
+def make_parts(parts):
+    """A list of parts as the C array of nr_part.  Each part is a dict (or a tuple in this order):
+    net, op ("union" / "subtract" or NR_PART_*; default union), rot (3 x 3, local -> world; default
+    identity), pos (default 0) and scale (default 1)."""
+    arr = (NRPart * len(parts))()
+    for a, p in zip(arr, parts):
+        if not isinstance(p, dict):
+            p = dict(zip(("net", "op", "rot", "pos", "scale"), p))
+        op = p.get("op", 0)
+        a.net = int(p.get("net", 0))
+        a.op = NR_PART_OP[op] if isinstance(op, str) else int(op)
+        a.rot[:] = [float(v) for v in np.asarray(p.get("rot", np.eye(3)), np.float32).reshape(9)]
+        a.pos[:] = [float(v) for v in np.asarray(p.get("pos", (0, 0, 0)), np.float32).reshape(3)]
+        a.scale = float(np.float32(p.get("scale", 1.0)))
+    return arr
+
+
+def compose_bound(parts, nnets):
+    """nr_compose_bound (host only): the parts checked as create checks them, and the world bound
+    (center float32 [3], radius float32) they give."""
+    arr = make_parts(parts)
+    c = np.zeros(3, np.float32)
+    r = ctypes.c_float(0)
+    check(lib().nr_compose_bound(arr, len(arr), int(nnets), _fptr(c), ctypes.byref(r)))
+    return c, np.float32(r.value)
+
+
+class Composition:
+    """nr_compose: up to 4 networks (Renderers with a fused network loaded) placed as up to 16 parts
+    and combined by union / subtraction, traced as one scene.  `owner` is the Renderer whose device,
+    stream, view, frame number, colour settings and matcap every call uses; the nets may be closed
+    afterwards, the composition must be closed before its owner."""
+
+    def __init__(self, owner, nets, parts):
+        self._L = lib()
+        self.owner = owner
+        self._c = ctypes.c_void_p()
+        nets = list(nets)
+        self.nnets = len(nets)
+        arr = (ctypes.c_void_p * max(len(nets), 1))(*[r._ctx.value for r in nets])
+        pa = make_parts(parts)
+        owner._chk(self._L.nr_compose_create(owner._ctx, arr, len(nets), pa, len(pa), ctypes.byref(self._c)))
+
+    def close(self):
+        if self._c:
+            # (the C object reaches through its owner: after an owner closed first it is left alone)
+            if self.owner._ctx:
+                self._L.nr_compose_destroy(self._c)
+            self._c = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _chk(self, rc):
+        return check(rc, self.owner._ctx)
+
+    def set_parts(self, parts):
+        """New transforms, ops or part count; the packs are not uploaded again."""
+        pa = make_parts(parts)
+        self._chk(self._L.nr_compose_set_parts(self._c, pa, len(pa)))
+        return self
+
+    def info(self):
+        nn, npart, c, r = ctypes.c_int(0), ctypes.c_int(0), np.zeros(3, np.float32), ctypes.c_float(0)
+        self._chk(self._L.nr_compose_info(self._c, ctypes.byref(nn), ctypes.byref(npart), _fptr(c), ctypes.byref(r)))
+        return {"nets": nn.value, "parts": npart.value, "center": c, "radius": np.float32(r.value)}
+
+    def sample(self, points, with_stats=False):
+        """The field at host points [n, 3]: {"value": float32 [n], "owner": int32 [n]}."""
+        P = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = P.shape[0]
+        out = {"value": np.zeros(n, np.float32), "owner": np.zeros(n, np.int32)}
+        st = NRComposeStats()
+        self._chk(self._L.nr_compose_sample(self._c, P.ctypes.data, n, out["value"].ctypes.data, out["owner"].ctypes.data,
+                                            NR_HOST, ctypes.byref(st) if with_stats else None))
+        return (out, st.as_dict()) if with_stats else out
+
+    @staticmethod
+    def _outputs(shape, normals):
+        out = Renderer._query_outputs(shape, normals)
+        out["part"] = np.zeros(shape, np.int32)
+        return out
+
+    def trace_rays(self, origins, dirs, max_steps=6000, normals=True, with_stats=False):
+        """nr_compose_trace_rays on host arrays: Renderer.trace_rays' dict plus "part", the part that
+        owns each hit (-1 for any other status)."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError(f"origins {o.shape} and dirs {d.shape} differ")
+        n = o.shape[0]
+        out = self._outputs((n,), normals)
+        st = NRComposeStats()
+        self._chk(self._L.nr_compose_trace_rays(self._c, o.ctypes.data, d.ctypes.data, n, int(max_steps),
+                                                *[a.ctypes.data if a is not None else None for a in out.values()], NR_HOST,
+                                                ctypes.byref(st) if with_stats else None))
+        if not normals:
+            del out["normal"]
+        return (out, st.as_dict()) if with_stats else out
+
+    def trace_rays_device(self, origins_ptr, dirs_ptr, n, max_steps=6000, status_ptr=None, steps_ptr=None, t_ptr=None,
+                          position_ptr=None, normal_ptr=None, part_ptr=None, with_stats=False):
+        """nr_compose_trace_rays on device buffers, on the owner's stream (Renderer.trace_rays_device)."""
+        vp = [ctypes.c_void_p(p) if p else None
+              for p in (origins_ptr, dirs_ptr, status_ptr, steps_ptr, t_ptr, position_ptr, normal_ptr, part_ptr)]
+        st = NRComposeStats()
+        self._chk(self._L.nr_compose_trace_rays(self._c, vp[0], vp[1], int(n), int(max_steps), *vp[2:], NR_DEVICE,
+                                                ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
+    def gbuffer(self, W, H, max_steps=6000, normals=True, with_stats=False):
+        """nr_compose_gbuffer: the trace_rays outputs for the W x H pixel rays of the owner's view,
+        shaped (H, W) and (H, W, 3)."""
+        out = self._outputs((H, W), normals)
+        st = NRComposeStats()
+        self._chk(self._L.nr_compose_gbuffer(self._c, W, H, int(max_steps),
+                                             *[a.ctypes.data if a is not None else None for a in out.values()], NR_HOST,
+                                             ctypes.byref(st) if with_stats else None))
+        if not normals:
+            del out["normal"]
+        return (out, st.as_dict()) if with_stats else out
+
+    def gbuffer_device(self, W, H, max_steps=6000, status_ptr=None, steps_ptr=None, t_ptr=None, position_ptr=None,
+                       normal_ptr=None, part_ptr=None, with_stats=False):
+        vp = [ctypes.c_void_p(p) if p else None for p in (status_ptr, steps_ptr, t_ptr, position_ptr, normal_ptr, part_ptr)]
+        st = NRComposeStats()
+        self._chk(self._L.nr_compose_gbuffer(self._c, int(W), int(H), int(max_steps), *vp, NR_DEVICE,
+                                             ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
+    def render(self, W, H, max_steps=6000, with_part=False, with_stats=True):
+        """nr_compose_render: the (H, W) uint32 frame in the owner's colouring; with_part adds the
+        (H, W) int32 owner map."""
+        img = np.zeros((H, W), np.uint32)
+        part = np.zeros((H, W), np.int32) if with_part else None
+        st = NRComposeStats()
+        self._chk(self._L.nr_compose_render(self._c, img.ctypes.data, W, H, int(max_steps),
+                                            part.ctypes.data if with_part else None, NR_HOST,
+                                            ctypes.byref(st) if with_stats else None))
+        res = (img,) + ((part,) if with_part else ()) + ((st.as_dict(),) if with_stats else ())
+        return res if len(res) > 1 else img

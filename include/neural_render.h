@@ -602,6 +602,93 @@ int nr_project_points(nr_ctx *ctx, const float *X /*[n][dims[0]]*/, long n, cons
                       float *distance /*[n]*/, int32_t *iters /*[n]*/, int32_t *status /*[n]*/,
                       int loc, nr_stats *stats);
 
+/* ---- composed scenes: several networks, placed and combined by CSG ---------------- */
+/* (new symbols and new structs only: NR_ABI_VERSION stays 3, nr_stats is unchanged)
+ *
+ * A composition holds copies of the fp32 packs of 1..NR_COMPOSE_MAX_NETS source contexts and
+ * 1..NR_COMPOSE_MAX_PARTS parts, each one network rotated, moved and uniformly scaled, folded in
+ * part order by union or subtraction.  It is created on an owner context, which supplies the device,
+ * the stream, the view, the frame number, the colour settings and the matcap at the time of each
+ * call; the owner needs no network of its own.  The source contexts may be destroyed after
+ * nr_compose_create; the composition must be destroyed before its owner.
+ *
+ * The field.  All arithmetic is f32, one rounding per operation, no contraction; dot3(a, b) =
+ * (a0 b0 + a1 b1) + a2 b2.  For a world point p and part j, with inv_s = 1.0f / scale:
+ *     v   = p - pos
+ *     q_k = ((v.x rot[0 + k] + v.y rot[3 + k]) + v.z rot[6 + k]) * inv_s,   k = 0, 1, 2
+ *     qq  = dot3(q, q)
+ *     d_j = qq <= 1.45f ? scale * tanh(net_j(q[, (float)frame]))    (NR_SCENE_TANH's value)
+ *                       : scale * (sqrtf(qq) - 1.19f)               (the bound's distance; a NaN qq too)
+ * and d = d_0, owner = 0; then for j = 1 .. nparts - 1: a union takes d_j where d_j < d, a subtraction
+ * takes -d_j where -d_j > d, and owner = j where it took.  A NaN comparison is false.  The network is
+ * only evaluated where qq <= 1.45: a part costs a ray far from it no evaluation.
+ *
+ * The bound.  centre c = the mean of the part positions (in double, rounded to f32); radius =
+ * max_j(|pos_j - c| (1 + 2^-20) + (double)(1.2f * scale_j)), rounded up to f32 (nr_compose_info).
+ *
+ * Rays.  The entry is nr_trace_rays' on o - c and radius * radius; tnear = max(tnear, 0), p = o + d *
+ * tnear, tfar = tfar - tnear (the remaining interval; the single-network calls keep the reference's
+ * unreduced tfar).  Each iteration: tstep = field(p); tfar -= tstep; tfar <= 0 -> ESCAPED; else p += d *
+ * tstep, travel += tstep, and tstep < 1e-6 -> HIT when an iteration is left, else LIMIT, as
+ * nr_trace_rays; t = tnear + travel.  A HIT's normal is the normalised tetrahedral gradient of the
+ * composed field at p (epsilon 1e-5); part[i] = the owner at the converging step, -1 for every other
+ * status.  A ray's results depend only on that ray. */
+#define NR_COMPOSE_MAX_NETS 4
+#define NR_COMPOSE_MAX_PARTS 16
+#define NR_PART_UNION 0
+#define NR_PART_SUBTRACT 1
+typedef struct nr_part {
+    int net;        /* index into the nets given at creation */
+    int op;         /* NR_PART_UNION, NR_PART_SUBTRACT; part 0 must be a union */
+    float rot[9];   /* row-major rotation, local -> world (orthonormal, det +1) */
+    float pos[3];   /* world position of the local origin */
+    float scale;    /* uniform, > 0 */
+} nr_part;
+typedef struct nr_compose nr_compose;
+typedef struct nr_compose_stats {
+    uint64_t ray_steps;    /* sum of the rays' steps (field evaluations of marching rays) */
+    uint64_t shade_evals;  /* 4 per HIT with normals, else 0 */
+    uint64_t rays_hit;     /* rays that entered the bound */
+    uint64_t rays_shaded;  /* HITs */
+    uint64_t part_evals;   /* (marching ray, part) pairs inside that part's bound: network evaluations a ray needed */
+    uint64_t wave_evals;   /* network evaluations issued, per wave (march, normals and samples); depends on the grouping */
+    uint64_t wave_skips;   /* (wave, part) pairs with no lane in bound: evaluations not issued; depends on the grouping */
+    int32_t iterations;    /* the largest steps */
+    int32_t launches;
+    float ms_total;
+} nr_compose_stats;
+/* Errors of create / set_parts, before any launch: NR_E_INVALID (a NULL argument, nnets outside
+ * 1..4, nparts outside 1..16, a net index out of range, part 0 not a union, an unknown op, a scale
+ * that is not finite or <= 0, max |R R^T - I| > 1e-4 or det < 0, a non-finite position, a source on
+ * another device, the packs and the per-wave lists over the LDS of a CU), NR_E_STATE (a source
+ * without a network), NR_E_FORMAT (a source whose network the fused kernels do not take). */
+int nr_compose_create(nr_ctx *owner, nr_ctx *const *nets, int nnets, const nr_part *parts, int nparts,
+                      nr_compose **out);
+int nr_compose_destroy(nr_compose *c);
+/* The checks create and set_parts make on the parts (for nnets networks) and the bound above, on the
+ * host alone: no context, no device.  center and radius may be NULL. */
+int nr_compose_bound(const nr_part *parts, int nparts, int nnets, float center[3], float *radius);
+/* New transforms, ops or part count; the packs stay where they are. */
+int nr_compose_set_parts(nr_compose *c, const nr_part *parts, int nparts);
+/* Any pointer may be NULL. */
+int nr_compose_info(const nr_compose *c, int *nnets, int *nparts, float center[3], float *radius);
+/* value[i] = the field at points[i], owner[i] = its owner; on the points of a lattice the values are
+ * what nr_mesh_grid takes.  n <= 2^30; n = 0 returns NR_OK without a launch. */
+int nr_compose_sample(nr_compose *c, const float *points /*[n][3]*/, long n, float *value /*[n]*/,
+                      int32_t *owner /*[n]*/, int loc, nr_compose_stats *stats);
+/* nr_trace_rays through the composed field (above); part [n] as the other outputs, any may be NULL. */
+int nr_compose_trace_rays(nr_compose *c, const float *origins /*[n][3]*/, const float *dirs /*[n][3]*/, long n,
+                          int max_steps, int32_t *status, int32_t *steps, float *t, float *position /*[n][3]*/,
+                          float *normal /*[n][3]*/, int32_t *part, int loc, nr_compose_stats *stats);
+/* The same for the W x H pixel rays of the owner's view (nr_render_gbuffer's rays); W * H <= 2^30. */
+int nr_compose_gbuffer(nr_compose *c, int W, int H, int max_steps, int32_t *status, int32_t *steps, float *t,
+                       float *position, float *normal, int32_t *part, int loc, nr_compose_stats *stats);
+/* The frame: a HIT pixel gets the owner's colouring (facing, or its matcap) of the composed normal,
+ * every other pixel 0 -- the geometry buffer and one colouring launch.  part (may be NULL) as above.
+ * NR_E_STATE for matcap colouring without a matcap. */
+int nr_compose_render(nr_compose *c, uint32_t *out /*W*H*/, int W, int H, int max_steps, int32_t *part /*W*H or NULL*/,
+                      int loc, nr_compose_stats *stats);
+
 /* One DenseLayer::forward (denseLayer.cu:229-278) on device buffers: layer l of the
  * loaded network applied to A [n][dims[l]] -> Z [n][dims[l+1]]. */
 int nr_layer_forward(nr_ctx *ctx, int layer, const float *A, float *Z, long n, int loc);
