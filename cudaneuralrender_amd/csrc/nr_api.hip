@@ -1727,11 +1727,20 @@ static int grid_launch(nr_ctx *c, const LatticeArgs &L, float *d_sdf, hipStream_
     return NR_OK;
 }
 
+// The brick samplers of a composed scene (k_compose_sp_coarse; sample: k_compose_sp_sample), one launch on s.
+static int compose_sparse_sampler(nr_compose *cp, const SparseArgs &A, bool sample, hipStream_t s);
+// The vertex pass of a composed scene (k_compose_vertex; defined with the nr_compose_* calls below):
+// normals and / or owners of the nv device vertices, one launch on s.
+static int compose_vertex_pass(nr_compose *cp, const float *d_vertices, float *d_normals, int32_t *d_part, size_t nv,
+                               hipStream_t s);
+
 // Count, scan and (with output buffers of sufficient capacity) emit over the device lattice d_sdf;
-// with `normals` the vertex normals too.  *launches counts the kernels issued.
+// with `normals` the vertex normals too.  cp: the lattice holds the composed field of cp (whose owner
+// is c): the normals are that field's and `part` (may be NULL) gets the vertices' owners.  *launches
+// counts the kernels issued.
 static int mesh_run(nr_ctx *c, const char *fn, hipStream_t s, const LatticeArgs &L, const float *d_sdf, float iso,
                     float *vertices, float *normals, long v_cap, int32_t *triangles, long t_cap, long *nv, long *nt,
-                    int loc, int *launches) {
+                    int loc, int *launches, nr_compose *cp = nullptr, int32_t *part = nullptr) {
     const size_t N = (size_t)L.n;
     const size_t nblk = (N + 255) / 256;
     // scratch, in 8-byte words: totals [2], scans [2][nblk], block counts [2][nblk] u32, point words [N] u32
@@ -1762,20 +1771,26 @@ static int mesh_run(nr_ctx *c, const char *fn, hipStream_t s, const LatticeArgs 
         return set_err(c, NR_E_NOMEM, "%s: %ld vertices / %ld triangles exceed the capacities %ld / %ld", fn, *nv, *nt,
                        v_cap, t_cap);
     if (tot[0] == 0) return NR_OK;  // (no crossing edge: no triangle either)
-    const size_t V3 = 3 * (size_t)tot[0], T3 = 3 * (size_t)tot[1];
+    const size_t NV = (size_t)tot[0], V3 = 3 * NV, T3 = 3 * (size_t)tot[1];
     float *dv = vertices, *dn = normals;
-    int32_t *dt = triangles;
+    int32_t *dt = triangles, *dp = part;
     if (loc != NR_DEVICE) {
-        if ((rc = ensure_buf(c, c->d_mio, c->cap_mio, V3 * (normals ? 2 : 1) + T3)) != NR_OK) return rc;
+        if ((rc = ensure_buf(c, c->d_mio, c->cap_mio, V3 * (normals ? 2 : 1) + T3 + (part ? NV : 0))) != NR_OK) return rc;
         dv = c->d_mio;
         dn = normals ? dv + V3 : nullptr;
         dt = reinterpret_cast<int32_t *>(dv + V3 * (normals ? 2 : 1));
+        dp = part ? dt + T3 : nullptr;
     }
     A.vertices = dv;
     A.triangles = dt;
     HIPCHK(c, launch_mesh_emit(A, s));
     *launches += 1;
-    if (normals) {
+    if (cp) {
+        if (dn || dp) {
+            if ((rc = compose_vertex_pass(cp, dv, dn, dp, NV, s)) != NR_OK) return rc;
+            *launches += 1;
+        }
+    } else if (normals) {
         VNormalArgs V{};
         V.vertices = dv;
         V.normals = dn;
@@ -1791,6 +1806,7 @@ static int mesh_run(nr_ctx *c, const char *fn, hipStream_t s, const LatticeArgs 
     if (loc != NR_DEVICE) {
         HIPCHK(c, hipMemcpyAsync(vertices, dv, V3 * 4, hipMemcpyDeviceToHost, s));
         if (normals) HIPCHK(c, hipMemcpyAsync(normals, dn, V3 * 4, hipMemcpyDeviceToHost, s));
+        if (part) HIPCHK(c, hipMemcpyAsync(part, dp, NV * 4, hipMemcpyDeviceToHost, s));
         if (T3) HIPCHK(c, hipMemcpyAsync(triangles, dt, T3 * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
     }
@@ -1886,24 +1902,34 @@ int nr_extract_mesh(nr_ctx *c, const float origin[3], const float step[3], const
 // ---- brick-sparse extraction (nr_sparse.hip) ----
 
 // ensure_buf for scratch whose size the lattice decides: a refused allocation is NR_E_NOMEM
-static int ensure_scratch(nr_ctx *c, const char *what, unsigned long long *&p, size_t &cap, size_t words) {
+static int ensure_scratch(nr_ctx *c, const char *fn, const char *what, unsigned long long *&p, size_t &cap, size_t words) {
     if (words <= cap) return NR_OK;
     dfree(p);
     cap = 0;
     if (hipMalloc(&p, words * 8) != hipSuccess) {
         (void)hipGetLastError();
         p = nullptr;
-        return set_err(c, NR_E_NOMEM, "nr_extract_mesh_sparse: cannot allocate %zu bytes of %s scratch", words * 8, what);
+        return set_err(c, NR_E_NOMEM, "%s: cannot allocate %zu bytes of %s scratch", fn, words * 8, what);
     }
     cap = words;
     return NR_OK;
 }
 
-int nr_extract_mesh_sparse(nr_ctx *c, const float origin[3], const float step[3], const int dims[3], float iso, int brick,
-                           float band, float *vertices, float *normals, int64_t *keys, long v_cap, int32_t *triangles,
-                           long t_cap, long *nv, long *nt, long *active_bricks, int loc, nr_stats *stats) {
-    const char *fn = "nr_extract_mesh_sparse";
-    if (!c) return set_err(nullptr, NR_E_INVALID, "%s: ctx is NULL", fn);
+// what a brick-sparse extraction did, for the caller's statistics
+struct SparseDone {
+    uint64_t points = 0;   // the brick-corner lattice plus the active bricks' point sets
+    uint64_t active = 0;
+    int launches = 0;
+    float ms = 0;
+};
+
+// nr_extract_mesh_sparse on c's stream and scratch.  cp == NULL: c's network and scene.  cp: the
+// composed field of cp (whose owner is c) in the two samplers and the vertex pass, which then
+// writes `part` too (may be NULL); the caller has zeroed cp's statistics.  timed: *done gets ms.
+static int sparse_run(nr_ctx *c, nr_compose *cp, const char *fn, const float origin[3], const float step[3], const int dims[3],
+                      float iso, int brick, float band, float *vertices, float *normals, int32_t *part, int64_t *keys,
+                      long v_cap, int32_t *triangles, long t_cap, long *nv, long *nt, long *active_bricks, int loc, bool timed,
+                      SparseDone *done) {
     if (!origin || !step || !dims || !nv || !nt) return set_err(c, NR_E_INVALID, "%s: NULL origin, step, dims, nv or nt", fn);
     *nv = 0;
     *nt = 0;
@@ -1915,6 +1941,7 @@ int nr_extract_mesh_sparse(nr_ctx *c, const float origin[3], const float step[3]
     if (!std::isfinite(iso)) return set_err(c, NR_E_INVALID, "%s: iso is not finite", fn);
     if (!vertices != !triangles) return set_err(c, NR_E_INVALID, "%s: vertices and triangles are given together", fn);
     if ((keys || normals) && !vertices) return set_err(c, NR_E_INVALID, "%s: keys and normals need vertices", fn);
+    if (part && !vertices) return set_err(c, NR_E_INVALID, "%s: part needs vertices", fn);
     SparseArgs A{};
     SparseLattice &L = A.L;
     for (int a = 0; a < 3; ++a) { L.origin[a] = origin[a]; L.step[a] = step[a]; }
@@ -1924,7 +1951,7 @@ int nr_extract_mesh_sparse(nr_ctx *c, const float origin[3], const float step[3]
     const unsigned long long nbricks = (unsigned long long)L.nbx * L.nby * L.nbz;
     if (nbricks > (1ull << 30)) return set_err(c, NR_E_INVALID, "%s: %llu bricks, more than 2^30", fn, nbricks);
     int rc;
-    if ((rc = fused_check(c, fn)) != NR_OK) return rc;
+    if (!cp && (rc = fused_check(c, fn)) != NR_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     GET_STREAM(c, s);
     L.nbricks = (uint32_t)nbricks;
@@ -1943,7 +1970,7 @@ int nr_extract_mesh_sparse(nr_ctx *c, const float origin[3], const float step[3]
     // per-brick scratch, in 8-byte words: totals [2], scans [2][nblk], block counts [2][nblk] u32, the
     // map [nbricks] i32, the corner values [ncoarse] f32
     const size_t nblk_b = ((size_t)L.nbricks + 255) / 256;
-    if ((rc = ensure_scratch(c, "per-brick", c->d_spb, c->cap_spb,
+    if ((rc = ensure_scratch(c, fn, "per-brick", c->d_spb, c->cap_spb,
                              2 + 2 * nblk_b + nblk_b + ((size_t)L.nbricks + 1) / 2 + ((size_t)L.ncoarse + 1) / 2)) != NR_OK)
         return rc;
     A.nblk_b = (int)nblk_b;
@@ -1955,7 +1982,11 @@ int nr_extract_mesh_sparse(nr_ctx *c, const float origin[3], const float step[3]
     const int cus = num_cus(c->device);
     const int bpc = c->blocks_per_cu > 0 ? c->blocks_per_cu : 12;  // as nr_sample_grid
     HIPCHK(c, hipEventRecord(c->ev0, s));
-    HIPCHK(c, launch_sparse_coarse(A, c->mlp16, (int)std::max<size_t>(1, std::min<size_t>(((size_t)L.ncoarse + 255) / 256, (size_t)cus * bpc)), s));
+    if (cp) {
+        if ((rc = compose_sparse_sampler(cp, A, false, s)) != NR_OK) return rc;
+    } else {
+        HIPCHK(c, launch_sparse_coarse(A, c->mlp16, (int)std::max<size_t>(1, std::min<size_t>(((size_t)L.ncoarse + 255) / 256, (size_t)cus * bpc)), s));
+    }
     HIPCHK(c, launch_sparse_classify_count(A, s));
     MeshArgs scan{};
     scan.nblk = A.nblk_b; scan.cnt = A.bcnt; scan.off = A.boff; scan.total = A.btotal;
@@ -1975,7 +2006,7 @@ int nr_extract_mesh_sparse(nr_ctx *c, const float origin[3], const float step[3]
         if (npts >= ((size_t)1 << 37))
             return set_err(c, NR_E_NOMEM, "%s: %u active bricks need more than 1 TiB of scratch", fn, A.nactive);
         const size_t nblk_m = (npts + 255) / 256;
-        if ((rc = ensure_scratch(c, "per-active-brick", c->d_spa, c->cap_spa,
+        if ((rc = ensure_scratch(c, fn, "per-active-brick", c->d_spa, c->cap_spa,
                                  2 + 2 * nblk_m + nblk_m + ((size_t)A.nactive + 1) / 2 + npts)) != NR_OK)
             return rc;
         A.nblk_m = (int)nblk_m;
@@ -1986,7 +2017,11 @@ int nr_extract_mesh_sparse(nr_ctx *c, const float origin[3], const float step[3]
         A.word = reinterpret_cast<uint32_t *>(c->d_spa + 2 + 3 * nblk_m + ((size_t)A.nactive + 1) / 2);
         A.store = reinterpret_cast<float *>(A.word + npts);
         HIPCHK(c, launch_sparse_classify_emit(A, s));
-        HIPCHK(c, launch_sparse_sample(A, c->mlp16, (int)std::max<size_t>(1, std::min<size_t>(nblk_m, (size_t)cus * bpc)), s));
+        if (cp) {
+            if ((rc = compose_sparse_sampler(cp, A, true, s)) != NR_OK) return rc;
+        } else {
+            HIPCHK(c, launch_sparse_sample(A, c->mlp16, (int)std::max<size_t>(1, std::min<size_t>(nblk_m, (size_t)cus * bpc)), s));
+        }
         HIPCHK(c, launch_sparse_mesh_count(A, s));
         scan.nblk = A.nblk_m; scan.cnt = A.cnt; scan.off = A.off; scan.total = A.total;
         HIPCHK(c, launch_mesh_scan(scan, s));
@@ -2005,21 +2040,27 @@ int nr_extract_mesh_sparse(nr_ctx *c, const float origin[3], const float step[3]
         const size_t NV = (size_t)mtot[0], V3 = 3 * NV, T3 = 3 * (size_t)mtot[1];
         float *dv = vertices, *dn = with_normals ? normals : nullptr;
         int64_t *dk = keys;
-        int32_t *dt = triangles;
+        int32_t *dt = triangles, *dp = part;
         if (loc != NR_DEVICE) {
-            // staging: keys (8-byte aligned) first, then vertices, normals, triangles
-            if ((rc = ensure_buf(c, c->d_mio, c->cap_mio, (keys ? 2 * NV : 0) + V3 * (with_normals ? 2 : 1) + T3)) != NR_OK) return rc;
+            // staging: keys (8-byte aligned) first, then vertices, normals, triangles, owners
+            if ((rc = ensure_buf(c, c->d_mio, c->cap_mio, (keys ? 2 * NV : 0) + V3 * (with_normals ? 2 : 1) + T3 + (part ? NV : 0))) != NR_OK) return rc;
             dk = keys ? reinterpret_cast<int64_t *>(c->d_mio) : nullptr;
             dv = c->d_mio + (keys ? 2 * NV : 0);
             dn = with_normals ? dv + V3 : nullptr;
             dt = reinterpret_cast<int32_t *>(dv + V3 * (with_normals ? 2 : 1));
+            dp = part ? dt + T3 : nullptr;
         }
         A.vertices = dv;
         A.keys = reinterpret_cast<long long *>(dk);
         A.triangles = dt;
         HIPCHK(c, launch_sparse_mesh_emit(A, s));
         launches += 1;
-        if (with_normals) {
+        if (cp) {
+            if (dn || dp) {
+                if ((rc = compose_vertex_pass(cp, dv, dn, dp, NV, s)) != NR_OK) return rc;
+                launches += 1;
+            }
+        } else if (with_normals) {
             VNormalArgs V{};
             V.vertices = dv;
             V.normals = dn;
@@ -2034,22 +2075,39 @@ int nr_extract_mesh_sparse(nr_ctx *c, const float origin[3], const float step[3]
             HIPCHK(c, hipMemcpyAsync(vertices, dv, V3 * 4, hipMemcpyDeviceToHost, s));
             if (with_normals) HIPCHK(c, hipMemcpyAsync(normals, dn, V3 * 4, hipMemcpyDeviceToHost, s));
             if (keys) HIPCHK(c, hipMemcpyAsync(keys, dk, NV * 8, hipMemcpyDeviceToHost, s));
+            if (part) HIPCHK(c, hipMemcpyAsync(part, dp, NV * 4, hipMemcpyDeviceToHost, s));
             if (T3) HIPCHK(c, hipMemcpyAsync(triangles, dt, T3 * 4, hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipStreamSynchronize(s));
         }
     }
     HIPCHK(c, hipEventRecord(c->ev1, s));
-    if (stats) {
+    done->points = (uint64_t)L.ncoarse + btot[1];
+    done->active = btot[0];
+    done->launches = launches;
+    if (timed) {
         HIPCHK(c, hipStreamSynchronize(s));
+        HIPCHK(c, hipEventElapsedTime(&done->ms, c->ev0, c->ev1));
+    }
+    return NR_OK;
+}
+
+int nr_extract_mesh_sparse(nr_ctx *c, const float origin[3], const float step[3], const int dims[3], float iso, int brick,
+                           float band, float *vertices, float *normals, int64_t *keys, long v_cap, int32_t *triangles,
+                           long t_cap, long *nv, long *nt, long *active_bricks, int loc, nr_stats *stats) {
+    const char *fn = "nr_extract_mesh_sparse";
+    if (!c) return set_err(nullptr, NR_E_INVALID, "%s: ctx is NULL", fn);
+    SparseDone done;
+    const int rc = sparse_run(c, nullptr, fn, origin, step, dims, iso, brick, band, vertices, normals, nullptr, keys, v_cap,
+                              triangles, t_cap, nv, nt, active_bricks, loc, stats != nullptr, &done);
+    if (rc != NR_OK) return rc;
+    if (stats) {
         nr_stats st{};
-        st.ray_steps = (uint64_t)L.ncoarse + btot[1];
-        st.rays_hit = btot[0];
+        st.ray_steps = done.points;
+        st.rays_hit = done.active;
         st.rays_shaded = (uint64_t)*nv;
-        st.shade_evals = with_normals ? 4ull * (uint64_t)*nv : 0ull;
-        st.launches = launches;
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        st.ms_total = ms;
+        st.shade_evals = normals && vertices ? 4ull * (uint64_t)*nv : 0ull;
+        st.launches = done.launches;
+        st.ms_total = done.ms;
         *stats = st;
     }
     return NR_OK;
@@ -2727,6 +2785,157 @@ int nr_compose_sample(nr_compose *cp, const float *points, long n, float *value,
     hs[0] = (unsigned long long)N;  // points evaluated
     compose_stats(hs, false, 2, ms, stats);
     return NR_OK;
+}
+
+// ---- composed scenes on a lattice (nr_compose_mesh.hip) ----
+
+// The ComposeArgs of the lattice kernels: the packs, nets and parts with the owner's frame and the
+// statistics words.  Their workgroup and grid are compose_shape's, over the points of the launch.
+static ComposeArgs compose_field_args(const nr_compose *cp) {
+    ComposeArgs Q = cp->A;
+    Q.frame = cp->owner->frame;
+    Q.stats = reinterpret_cast<unsigned long long *>(cp->d_cs + 32);
+    return Q;
+}
+
+static int compose_sparse_sampler(nr_compose *cp, const SparseArgs &A, bool sample, hipStream_t s) {
+    nr_ctx *c = cp->owner;
+    const ComposeArgs Q = compose_field_args(cp);
+    int threads, grid;
+    compose_shape(cp, sample ? (size_t)A.nactive * A.L.stride : (size_t)A.L.ncoarse, threads, grid);
+    if (sample) HIPCHK(c, launch_compose_sp_sample(Q, A, grid, threads, s));
+    else HIPCHK(c, launch_compose_sp_coarse(Q, A, grid, threads, s));
+    return NR_OK;
+}
+
+static int compose_vertex_pass(nr_compose *cp, const float *d_vertices, float *d_normals, int32_t *d_part, size_t nv,
+                               hipStream_t s) {
+    nr_ctx *c = cp->owner;
+    ComposeVertexArgs V{};
+    V.vertices = d_vertices;
+    V.normals = d_normals;
+    V.part = d_part;
+    V.nv = (long)nv;
+    int threads, grid;
+    compose_shape(cp, nv, threads, grid);
+    HIPCHK(c, launch_compose_vertex(compose_field_args(cp), V, grid, threads, s));
+    return NR_OK;
+}
+
+// one k_compose_grid launch over the lattice (the statistics zeroed before it: two launches)
+static int compose_grid_launch(nr_compose *cp, const LatticeArgs &L, float *d_value, int32_t *d_owner, hipStream_t s) {
+    nr_ctx *c = cp->owner;
+    ComposeGridArgs G{};
+    G.L = L;
+    G.value = d_value;
+    G.owner = d_owner;
+    int threads, grid;
+    compose_shape(cp, (size_t)L.n, threads, grid);
+    HIPCHK(c, hipMemsetAsync(cp->d_cs, 0, COMPOSE_CS_BYTES, s));
+    HIPCHK(c, launch_compose_grid(compose_field_args(cp), G, grid, threads, s));
+    return NR_OK;
+}
+
+// the statistics of a lattice call: the device words [4..6] and what the host knows
+static int compose_lattice_stats(nr_compose *cp, hipStream_t s, uint64_t points, uint64_t active, long nv, bool normals,
+                                 bool part, int launches, float ms, nr_compose_stats *stats) {
+    nr_ctx *c = cp->owner;
+    unsigned long long hs[7];
+    HIPCHK(c, hipMemcpyAsync(hs, reinterpret_cast<unsigned long long *>(cp->d_cs + 32), sizeof hs, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    nr_compose_stats st{};
+    st.ray_steps = points;
+    st.rays_hit = active;
+    st.rays_shaded = (uint64_t)nv;
+    st.shade_evals = (normals ? 4ull * (uint64_t)nv : 0ull) + (part ? (uint64_t)nv : 0ull);
+    st.part_evals = hs[4];
+    st.wave_evals = hs[5];
+    st.wave_skips = hs[6];
+    st.launches = launches;
+    st.ms_total = ms;
+    *stats = st;
+    return NR_OK;
+}
+
+int nr_compose_sample_grid(nr_compose *cp, const float origin[3], const float step[3], const int dims[3], float *value,
+                           int32_t *owner, int loc, nr_compose_stats *stats) {
+    const char *fn = "nr_compose_sample_grid";
+    if (!cp) return set_err(nullptr, NR_E_INVALID, "%s: composition is NULL", fn);
+    nr_ctx *c = cp->owner;
+    if (!value && !owner) return set_err(c, NR_E_INVALID, "%s: value and owner are both NULL", fn);
+    int rc;
+    if ((rc = lattice_check(c, fn, origin, step, dims, 1)) != NR_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const LatticeArgs L = make_lattice(origin, step, dims);
+    const size_t N = (size_t)L.n;
+    float *dv = value;
+    int32_t *dw = owner;
+    if (loc != NR_DEVICE) {
+        if ((rc = ensure_buf(c, cp->d_io, cp->cap_io, (value ? N : 0) + (owner ? N : 0))) != NR_OK) return rc;
+        dv = value ? cp->d_io : nullptr;
+        dw = owner ? reinterpret_cast<int32_t *>(cp->d_io + (value ? N : 0)) : nullptr;
+    }
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    if ((rc = compose_grid_launch(cp, L, dv, dw, s)) != NR_OK) return rc;
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (loc != NR_DEVICE) {
+        if (value) HIPCHK(c, hipMemcpyAsync(value, dv, N * 4, hipMemcpyDeviceToHost, s));
+        if (owner) HIPCHK(c, hipMemcpyAsync(owner, dw, N * 4, hipMemcpyDeviceToHost, s));
+    }
+    float ms = 0.0f;
+    if ((rc = end_timed(c, stats != nullptr, loc, s, &ms)) != NR_OK || !stats) return rc;
+    return compose_lattice_stats(cp, s, N, 0, 0, false, false, 2, ms, stats);
+}
+
+int nr_compose_extract_mesh(nr_compose *cp, const float origin[3], const float step[3], const int dims[3], float iso,
+                            float *vertices, float *normals, int32_t *part, long v_cap, int32_t *triangles, long t_cap,
+                            long *nv, long *nt, int loc, nr_compose_stats *stats) {
+    const char *fn = "nr_compose_extract_mesh";
+    if (!cp) return set_err(nullptr, NR_E_INVALID, "%s: composition is NULL", fn);
+    nr_ctx *c = cp->owner;
+    if (!nv || !nt) return set_err(c, NR_E_INVALID, "%s: NULL nv or nt", fn);
+    *nv = 0;
+    *nt = 0;
+    int rc;
+    if ((rc = lattice_check(c, fn, origin, step, dims, 2)) != NR_OK) return rc;
+    if (!std::isfinite(iso)) return set_err(c, NR_E_INVALID, "%s: iso is not finite", fn);
+    if (!vertices != !triangles) return set_err(c, NR_E_INVALID, "%s: vertices and triangles are given together", fn);
+    if ((normals || part) && !vertices) return set_err(c, NR_E_INVALID, "%s: normals and part need vertices", fn);
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const LatticeArgs L = make_lattice(origin, step, dims);
+    if ((rc = ensure_buf(c, c->d_grid, c->cap_grid, (size_t)L.n)) != NR_OK) return rc;
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    if ((rc = compose_grid_launch(cp, L, c->d_grid, nullptr, s)) != NR_OK) return rc;
+    int launches = 2;
+    if ((rc = mesh_run(c, fn, s, L, c->d_grid, iso, vertices, normals, v_cap, triangles, t_cap, nv, nt, loc, &launches, cp,
+                       part)) != NR_OK)
+        return rc;
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (!stats) return NR_OK;
+    HIPCHK(c, hipStreamSynchronize(s));
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    return compose_lattice_stats(cp, s, (uint64_t)L.n, 0, *nv, normals != nullptr, part != nullptr, launches, ms, stats);
+}
+
+int nr_compose_extract_mesh_sparse(nr_compose *cp, const float origin[3], const float step[3], const int dims[3], float iso,
+                                   int brick, float band, float *vertices, float *normals, int32_t *part, int64_t *keys,
+                                   long v_cap, int32_t *triangles, long t_cap, long *nv, long *nt, long *active_bricks,
+                                   int loc, nr_compose_stats *stats) {
+    const char *fn = "nr_compose_extract_mesh_sparse";
+    if (!cp) return set_err(nullptr, NR_E_INVALID, "%s: composition is NULL", fn);
+    nr_ctx *c = cp->owner;
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    HIPCHK(c, hipMemsetAsync(cp->d_cs, 0, COMPOSE_CS_BYTES, s));
+    SparseDone done;
+    const int rc = sparse_run(c, cp, fn, origin, step, dims, iso, brick, band, vertices, normals, part, keys, v_cap, triangles,
+                              t_cap, nv, nt, active_bricks, loc, stats != nullptr, &done);
+    if (rc != NR_OK || !stats) return rc;
+    return compose_lattice_stats(cp, s, done.points, done.active, *nv, normals && vertices, part && vertices,
+                                 done.launches + 1, done.ms, stats);
 }
 
 int nr_layer_forward(nr_ctx *c, int layer, const float *A, float *Z, long n, int loc) {

@@ -5,7 +5,8 @@
 //
 // k_compose is k_query's tracer (nr_query.hip: lanes refilled from a ray cursor, the tail packed
 // into the lowest tiles, converged rays waiting in a per-wave LDS list for 16-ray x 4-sample normal
-// passes, one set of statistics atomics per wave) with the field below in the place of one MLP:
+// passes, one set of statistics atomics per wave) with the composed field (nr_compose_field.h) in
+// the place of one MLP:
 //   * every distinct fp32 pack is staged once per workgroup into dynamic LDS, back to back (four of
 //     them are about 122 KB: one workgroup per CU, launched with 12 waves so that a SIMD holds three);
 //   * the part table is in the kernarg segment, the part loop is wave-uniform, and a part's network
@@ -14,6 +15,7 @@
 //   * a ray writes only its own slots and nothing it computes depends on another ray (the MLP's
 //     tiles are column-independent, its clamped and add + max forms bit-identical within the
 //     bound), so the outputs are the same for any workgroup size, grid or ray order.
+#include "nr_compose_field.h"
 #include "nr_mlp16.h"
 
 namespace nr {
@@ -23,60 +25,6 @@ constexpr int NR_COMPOSE_REFILL_MIN = 4;
 // converged rays waiting for their normal, per wave: a pass leaves at most 15, an iteration adds at most 64
 constexpr int CSTASH = 80;
 static_assert(16 - 1 + 64 <= CSTASH, "the per-wave list of converged rays");
-// the largest workgroup: 12 waves, three per SIMD, which is also what bounds the registers
-constexpr int NR_COMPOSE_MAX_THREADS = 768;
-
-// what a wave adds to the statistics while it evaluates the field
-struct FieldCount {
-    uint32_t pairs;  // (live lane, part) pairs in bound
-    uint32_t evals;  // network evaluations issued
-    uint32_t skips;  // parts with no lane in bound
-};
-
-// The composed field at p (neural_render.h: q = R^T (p - pos) / scale per part, the network where
-// qq <= 1.45, the bound's distance elsewhere, folded in part order), shared by the march, the normal
-// passes and k_compose_sample.  live: the lane holds a point; the others feed the networks zeros and
-// their result means nothing.  lds: the staged packs.
-__device__ __forceinline__ float compose_field(const ComposeArgs &C, const float *lds, float fr, F3 p, bool live,
-                                               int &owner, FieldCount &cnt) {
-    float d = 0.0f;
-    int own = 0;
-    for (int j = 0; j < C.nparts; ++j) {
-        const ComposePart &P = C.parts[j];
-        const F3 v = mk3(p.x - P.pos[0], p.y - P.pos[1], p.z - P.pos[2]);
-        const F3 q = mk3(((v.x * P.rot[0] + v.y * P.rot[3]) + v.z * P.rot[6]) * P.inv_s,
-                         ((v.x * P.rot[1] + v.y * P.rot[4]) + v.z * P.rot[7]) * P.inv_s,
-                         ((v.x * P.rot[2] + v.y * P.rot[5]) + v.z * P.rot[8]) * P.inv_s);
-        const float qq = dot3(q, q);
-        const bool inb = live && qq <= 1.45f;
-        const uint64_t m = __ballot(inb);
-        float sdf = 0.0f;
-        if (m) {
-            const ComposeNet &N = C.nets[P.net];
-            // lanes out of bound feed a finite point and discard the result
-            const F3 qi = inb ? q : mk3(0.0f, 0.0f, 0.0f);
-            const bool cl = N.f32_clamp && inputs_in_bound_f32(qi.x, qi.y, qi.z, fr);
-            sdf = mlp16_fp32(lds + N.off, N.in0, N.nh, fr, qi.x, qi.y, qi.z, tiles_of(m), cl);
-            cnt.evals += 1;
-            cnt.pairs += (uint32_t)__popcll(m);
-        } else {
-            cnt.skips += 1;
-        }
-        float dj;
-        if (inb) dj = P.scale * nr_tanh(sdf);
-        else dj = P.scale * (sqrtf(qq) - 1.19f);  // (a NaN qq lands here)
-        if (j == 0) {
-            d = dj;
-        } else if (P.op == NR_PART_SUBTRACT) {
-            const float nd = -dj;
-            if (nd > d) { d = nd; own = j; }
-        } else {
-            if (dj < d) { d = dj; own = j; }
-        }
-    }
-    owner = own;
-    return d;
-}
 
 // intersect_bounding (nr_device.h) against the sphere (c, r): the same expressions on Q = o - c and r2 = r * r
 __device__ __forceinline__ bool compose_intersect(F3 o, F3 d, const ComposeArgs &C, float &tnear, float &tfar) {
@@ -91,15 +39,6 @@ __device__ __forceinline__ bool compose_intersect(F3 o, F3 d, const ComposeArgs 
     tnear = (-b - sq) / a2;
     tfar = (-b + sq) / a2;
     return true;
-}
-
-// the packs into dynamic LDS, block-wide 16-byte copies
-__device__ __forceinline__ const float *compose_stage(const ComposeArgs &C) {
-    const int4 *src = reinterpret_cast<const int4 *>(C.packs);
-    int4 *dst = reinterpret_cast<int4 *>(nr_smem16);
-    for (int i = threadIdx.x; i < C.pack_bytes / 16; i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
-    return reinterpret_cast<const float *>(nr_smem16);
 }
 
 // k_compose<true>'s copy of the view in LDS
@@ -230,13 +169,7 @@ __global__ __launch_bounds__(NR_COMPOSE_MAX_THREADS) void k_compose(ComposeArgs 
             const int e = nstash - nb + (k < nb ? k : 0);
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             const float4 sp = stash[e];
-            // tetrahedron point q (c_tet): x = +1 for q = 0, 3; y = +1 for q = 2, 3; z = +1 for q = 1, 3
-            int qo = q4;
-            asm volatile("" : "+v"(qo));
-            const F3 tp = mk3((qo == 0 || qo == 3) ? 1.0f : -1.0f, qo >= 2 ? 1.0f : -1.0f, (qo & 1) ? 1.0f : -1.0f);
-            const F3 pq = add3(mk3(sp.x, sp.y, sp.z), mul3s(tp, NORMAL_EPSILON));
-            int own;
-            const F3 cq = mul3s(tp, compose_field(C, lds, fr, pq, k < nb, own, other));
+            const F3 cq = compose_tet_term(C, lds, fr, mk3(sp.x, sp.y, sp.z), q4, k < nb, other);
             const F3 c1 = quad_bcast3_1(cq), c2 = quad_bcast3_2(cq), c3 = quad_bcast3_3(cq);
             if (k < nb && q4 == 0) {
                 const F3 nrm = normalize3(add3(add3(add3(cq, c1), c2), c3));

@@ -329,6 +329,29 @@ hipError_t launch_compose_sample(const ComposeArgs &C, int grid, hipStream_t st)
 // colours the HIT pixels of a W x H geometry buffer (A: W, H, out, view, colouring), 0 elsewhere
 hipError_t launch_compose_color(const RenderArgs &A, const int32_t *status, const float *normal, hipStream_t st);
 
+// Composed-scene lattices and meshes (nr_compose_mesh.hip; nr_compose_sample_grid,
+// nr_compose_extract_mesh, nr_compose_extract_mesh_sparse).  The ComposeArgs of these launches carry
+// the packs, nets, parts, frame and stats ([4] in-bound (lattice point, part) pairs of the sampling
+// passes, [5] wave evaluations issued, [6] skipped); the workgroup is k_compose's (threads: 256, 512
+// or 768) and its dynamic LDS the packs alone.
+struct ComposeGridArgs {
+    LatticeArgs L;
+    float *value;                 // [n] or NULL
+    int32_t *owner;               // [n] or NULL
+};
+struct ComposeVertexArgs {
+    const float *vertices;        // [nv][3]
+    float *normals;               // [nv][3] or NULL: the normalised tetrahedral gradient of the composed field
+    int32_t *part;                // [nv] or NULL: the owner of the field at the vertex
+    long nv;
+};
+struct SparseArgs;
+hipError_t launch_compose_grid(const ComposeArgs &C, const ComposeGridArgs &G, int grid, int threads, hipStream_t st);
+hipError_t launch_compose_vertex(const ComposeArgs &C, const ComposeVertexArgs &V, int grid, int threads, hipStream_t st);
+// k_sp_coarse / k_sp_sample with the composed field (A.scene and A.frame are not read: C.frame)
+hipError_t launch_compose_sp_coarse(const ComposeArgs &C, const SparseArgs &A, int grid, int threads, hipStream_t st);
+hipError_t launch_compose_sp_sample(const ComposeArgs &C, const SparseArgs &A, int grid, int threads, hipStream_t st);
+
 int dense_lds_bytes(int in, int out);
 int grad_lds_bytes(const MlpArgs &M, const GradArgs &G);  // one k_grad workgroup's dynamic LDS
 hipError_t launch_grad(const GradArgs &G, const MlpArgs &M, int grid, hipStream_t st);  // 4-wave workgroups

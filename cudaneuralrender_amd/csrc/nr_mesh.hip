@@ -14,6 +14,7 @@
 // block's totals), k_mesh_scan (exclusive scan of the block totals, one workgroup) and k_mesh_emit
 // (every point writes its vertices and its cell's triangles at the scanned positions).  No atomic
 // decides an order: the output is a pure function of the inputs.
+#include "nr_lattice.h"
 #include "nr_mesh_rule.h"
 #include "nr_mlp16.h"
 
@@ -25,17 +26,6 @@ namespace nr {
 #endif
 
 static __constant__ MeshRule c_mesh_rule = make_mesh_rule();
-
-// (i, j, k) of linear index p
-__device__ __forceinline__ void lattice_ijk(const LatticeArgs &L, uint32_t p, int &i, int &j, int &k) {
-    const uint32_t nxy = (uint32_t)L.nx * (uint32_t)L.ny;
-    const uint32_t kk = udiv_r(p, nxy, L.inv_nxy);
-    const uint32_t r = p - kk * nxy;
-    const uint32_t jj = udiv_r(r, (uint32_t)L.nx, L.inv_nx);
-    i = (int)(r - jj * (uint32_t)L.nx);
-    j = (int)jj;
-    k = (int)kk;
-}
 
 // ---------------------------------------------------------------- sampler
 // Persistent waves deal the 64-point chunks of the linear index grid-stride; the fp32 pack is staged

@@ -20,6 +20,7 @@
 // holds both its ends (at most 8 candidates in the map; the brick that uses it is one).  No atomic
 // decides an order: the output is a pure function of the inputs.
 #include "nr_internal.h"
+#include "nr_lattice.h"
 #include "nr_mesh_rule.h"
 #include "nr_mlp16.h"
 
@@ -31,45 +32,6 @@ namespace nr {
 #endif
 
 static __constant__ MeshRule c_sp_rule = make_mesh_rule();
-
-struct Brick {
-    int b[3];  // brick coordinates
-    int e[3];  // cells along each axis, 1..B (the last brick of an axis may be ragged)
-};
-
-__device__ __forceinline__ Brick brick_of(const SparseLattice &L, uint32_t idx) {
-    Brick K;
-    const uint32_t nbxy = (uint32_t)L.nbx * (uint32_t)L.nby;
-    const uint32_t bz = udiv_r(idx, nbxy, L.inv_nbxy);
-    const uint32_t r = idx - bz * nbxy;
-    const uint32_t by = udiv_r(r, (uint32_t)L.nbx, L.inv_nbx);
-    K.b[0] = (int)(r - by * (uint32_t)L.nbx);
-    K.b[1] = (int)by;
-    K.b[2] = (int)bz;
-    K.e[0] = min(L.B, L.nx - 1 - L.B * K.b[0]);
-    K.e[1] = min(L.B, L.ny - 1 - L.B * K.b[1]);
-    K.e[2] = min(L.B, L.nz - 1 - L.B * K.b[2]);
-    return K;
-}
-
-__device__ __forceinline__ uint32_t brick_index(const SparseLattice &L, int bx, int by, int bz) {
-    return ((uint32_t)bz * (uint32_t)L.nby + (uint32_t)by) * (uint32_t)L.nbx + (uint32_t)bx;
-}
-
-// (li, lj, lk) of local index r < S^3
-__device__ __forceinline__ void local_ijk(const SparseLattice &L, uint32_t r, int &li, int &lj, int &lk) {
-    const uint32_t ss = (uint32_t)(L.S * L.S);
-    const uint32_t kk = udiv_r(r, ss, L.inv_ss);
-    const uint32_t q = r - kk * ss;
-    const uint32_t jj = udiv_r(q, (uint32_t)L.S, L.inv_s);
-    li = (int)(q - jj * (uint32_t)L.S);
-    lj = (int)jj;
-    lk = (int)kk;
-}
-
-__device__ __forceinline__ F3 lattice_point(const SparseLattice &L, int i, int j, int k) {
-    return mk3(L.origin[0] + (float)i * L.step[0], L.origin[1] + (float)j * L.step[1], L.origin[2] + (float)k * L.step[2]);
-}
 
 // ---------------------------------------------------------------- coarse sampler
 __global__ __launch_bounds__(256, NR_SPARSE_WPS) void k_sp_coarse(SparseArgs A, MlpArgs M) {
@@ -87,13 +49,7 @@ __global__ __launch_bounds__(256, NR_SPARSE_WPS) void k_sp_coarse(SparseArgs A, 
         const uint32_t base = c << 6, idx = base + (uint32_t)lane;
         const bool live = idx < n;
         F3 p = mk3(0.0f, 0.0f, 0.0f);
-        if (live) {
-            const uint32_t ck = udiv_r(idx, cxy, L.inv_cxy);
-            const uint32_t r = idx - ck * cxy;
-            const uint32_t cj = udiv_r(r, cx, L.inv_cx);
-            const uint32_t ci = r - cj * cx;
-            p = lattice_point(L, min(L.B * (int)ci, L.nx - 1), min(L.B * (int)cj, L.ny - 1), min(L.B * (int)ck, L.nz - 1));
-        }
+        if (live) p = corner_point(L, idx, cx, cxy);
         const uint32_t rem = n - base;
         const uint32_t tmask = rem >= 64u ? 0xfu : (1u << ((rem + 15u) >> 4)) - 1u;
         float sdf = mlp16_fp32(M, S.s32, fr, p.x, p.y, p.z, tmask);

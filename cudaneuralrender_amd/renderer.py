@@ -1020,3 +1020,125 @@ class Composition:
                                             ctypes.byref(st) if with_stats else None))
         res = (img,) + ((part,) if with_part else ()) + ((st.as_dict(),) if with_stats else ())
         return res if len(res) > 1 else img
+
+    # -- lattice sampling / isosurface extraction of the composed field
+    def sample_grid(self, origin, step, dims, owner=False, with_stats=False):
+        """nr_compose_sample_grid: the composed field at the lattice points origin + (i, j, k) * step,
+        dims = (nx, ny, nz), generated in the kernel.  Returns float32 [nz, ny, nx]; with owner=True
+        (value, owner int32 [nz, ny, nx])."""
+        o, s, d = _lattice(origin, step, dims)
+        val = np.zeros((d[2], d[1], d[0]), np.float32)
+        own = np.zeros((d[2], d[1], d[0]), np.int32) if owner else None
+        st = NRComposeStats()
+        self._chk(self._L.nr_compose_sample_grid(self._c, _fptr(o), _fptr(s), d, val.ctypes.data,
+                                                 own.ctypes.data if owner else None, NR_HOST,
+                                                 ctypes.byref(st) if with_stats else None))
+        res = (val,) + ((own,) if owner else ()) + ((st.as_dict(),) if with_stats else ())
+        return res if len(res) > 1 else val
+
+    def sample_grid_device(self, origin, step, dims, value_ptr=None, owner_ptr=None, with_stats=False):
+        """nr_compose_sample_grid into device buffers of nx * ny * nz float32 / int32 (at least one), on
+        the owner's stream."""
+        o, s, d = _lattice(origin, step, dims)
+        vp = [ctypes.c_void_p(p) if p else None for p in (value_ptr, owner_ptr)]
+        st = NRComposeStats()
+        self._chk(self._L.nr_compose_sample_grid(self._c, _fptr(o), _fptr(s), d, vp[0], vp[1], NR_DEVICE,
+                                                 ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
+    def extract_mesh(self, origin, step, dims, iso=0.0, normals=True, part=False, with_stats=False):
+        """nr_compose_extract_mesh: sample the composed field on the lattice and mesh it.  Returns
+        Renderer.extract_mesh's dict ("vertices", "triangles", "normals" as asked) plus, with
+        part=True, "part" [nv] int32: the part that owns the field at each vertex.  The count-only
+        call comes first (it samples the lattice too), then the buffers are allocated."""
+        o, s, d = _lattice(origin, step, dims)
+        nv, nt = ctypes.c_long(0), ctypes.c_long(0)
+        st = NRComposeStats()
+
+        def call(V, N, P, T):
+            return self._L.nr_compose_extract_mesh(
+                self._c, _fptr(o), _fptr(s), d, float(iso), None if V is None else V.ctypes.data,
+                None if N is None else N.ctypes.data, None if P is None else P.ctypes.data, 0 if V is None else V.shape[0],
+                None if T is None else T.ctypes.data, 0 if T is None else T.shape[0], ctypes.byref(nv), ctypes.byref(nt),
+                NR_HOST, ctypes.byref(st) if with_stats else None)
+
+        self._chk(call(None, None, None, None))
+        V, T = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
+        N = np.zeros((nv.value, 3), np.float32) if normals else None
+        P = np.zeros((nv.value,), np.int32) if part else None
+        if nv.value:
+            self._chk(call(V, N, P, T))
+        out = {"vertices": V, "triangles": T}
+        if normals:
+            out["normals"] = N
+        if part:
+            out["part"] = P
+        return (out, st.as_dict()) if with_stats else out
+
+    def extract_mesh_device(self, origin, step, dims, vertices_ptr, v_cap, triangles_ptr, t_cap, iso=0.0, normals_ptr=None,
+                            part_ptr=None, with_stats=False):
+        """nr_compose_extract_mesh into device buffers (v_cap x 3 float32 vertices and normals, v_cap
+        int32 owners, t_cap x 3 int32 triangles; vertices_ptr and triangles_ptr both None: count only),
+        on the owner's stream.  Returns (nv, nt), with the stats dict appended with_stats=True; short
+        capacities raise NRError with nothing written."""
+        o, s, d = _lattice(origin, step, dims)
+        vp = [ctypes.c_void_p(p) if p else None for p in (vertices_ptr, normals_ptr, part_ptr, triangles_ptr)]
+        nv, nt = ctypes.c_long(0), ctypes.c_long(0)
+        st = NRComposeStats()
+        self._chk(self._L.nr_compose_extract_mesh(self._c, _fptr(o), _fptr(s), d, float(iso), vp[0], vp[1], vp[2], int(v_cap),
+                                                  vp[3], int(t_cap), ctypes.byref(nv), ctypes.byref(nt), NR_DEVICE,
+                                                  ctypes.byref(st) if with_stats else None))
+        res = (nv.value, nt.value)
+        return res + (st.as_dict(),) if with_stats else res
+
+    def extract_mesh_sparse(self, origin, step, dims, iso=0.0, brick=8, band=None, normals=True, part=False, keys=True,
+                            with_stats=False):
+        """nr_compose_extract_mesh_sparse: extract_mesh restricted to the bricks of brick^3 cells that
+        have a corner within `band` of iso (or a sign change, or a NaN).  band=None is the brick's
+        diagonal, as Renderer.extract_mesh_sparse; too small a band leaves holes.  Returns that
+        method's dict ("vertices", "triangles", "active_bricks", "normals" and "keys" as asked) plus,
+        with part=True, "part" [nv] int32."""
+        o, s, d = _lattice(origin, step, dims)
+        bandf = self.owner._sparse_band(s, brick, band)
+        nv, nt, na = ctypes.c_long(0), ctypes.c_long(0), ctypes.c_long(0)
+        st = NRComposeStats()
+
+        def call(V, N, P, K, T):
+            return self._L.nr_compose_extract_mesh_sparse(
+                self._c, _fptr(o), _fptr(s), d, float(iso), int(brick), bandf,
+                None if V is None else V.ctypes.data, None if N is None else N.ctypes.data,
+                None if P is None else P.ctypes.data, None if K is None else K.ctypes.data, 0 if V is None else V.shape[0],
+                None if T is None else T.ctypes.data, 0 if T is None else T.shape[0],
+                ctypes.byref(nv), ctypes.byref(nt), ctypes.byref(na), NR_HOST, ctypes.byref(st) if with_stats else None)
+
+        self._chk(call(None, None, None, None, None))
+        V, T = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
+        N = np.zeros((nv.value, 3), np.float32) if normals else None
+        P = np.zeros((nv.value,), np.int32) if part else None
+        K = np.zeros((nv.value,), np.int64) if keys else None
+        if nv.value:
+            self._chk(call(V, N, P, K, T))
+        out = {"vertices": V, "triangles": T, "active_bricks": na.value}
+        if normals:
+            out["normals"] = N
+        if part:
+            out["part"] = P
+        if keys:
+            out["keys"] = K
+        return (out, st.as_dict()) if with_stats else out
+
+    def extract_mesh_sparse_device(self, origin, step, dims, vertices_ptr, v_cap, triangles_ptr, t_cap, iso=0.0, brick=8,
+                                   band=None, normals_ptr=None, part_ptr=None, keys_ptr=None, with_stats=False):
+        """nr_compose_extract_mesh_sparse into device buffers, shaped like
+        Renderer.extract_mesh_sparse_device with the v_cap int32 owners added.  Returns
+        (nv, nt, active_bricks), with the stats dict appended with_stats=True."""
+        o, s, d = _lattice(origin, step, dims)
+        vp = [ctypes.c_void_p(p) if p else None for p in (vertices_ptr, normals_ptr, part_ptr, keys_ptr, triangles_ptr)]
+        nv, nt, na = ctypes.c_long(0), ctypes.c_long(0), ctypes.c_long(0)
+        st = NRComposeStats()
+        self._chk(self._L.nr_compose_extract_mesh_sparse(
+            self._c, _fptr(o), _fptr(s), d, float(iso), int(brick), self.owner._sparse_band(s, brick, band), vp[0], vp[1],
+            vp[2], vp[3], int(v_cap), vp[4], int(t_cap), ctypes.byref(nv), ctypes.byref(nt), ctypes.byref(na), NR_DEVICE,
+            ctypes.byref(st) if with_stats else None))
+        res = (nv.value, nt.value, na.value)
+        return res + (st.as_dict(),) if with_stats else res

@@ -689,6 +689,74 @@ int nr_compose_gbuffer(nr_compose *c, int W, int H, int max_steps, int32_t *stat
 int nr_compose_render(nr_compose *c, uint32_t *out /*W*H*/, int W, int H, int max_steps, int32_t *part /*W*H or NULL*/,
                       int loc, nr_compose_stats *stats);
 
+/* ---- composed scenes: lattice sampling and mesh extraction ------------------------- */
+/* (new symbols only: NR_ABI_VERSION stays 3, nr_stats and nr_compose_stats are unchanged)
+ *
+ * nr_sample_grid, nr_extract_mesh and nr_extract_mesh_sparse for a composition: the same lattice, the
+ * same mesh rule, the composed field (above) in the place of sceneSDF(p, mlp(p)).
+ *  1. Lattice.  nr_sample_grid's: index (k * ny + j) * nx + i, coordinate origin[a] + (float)idx_a *
+ *     step[a] (one f32 multiply, then one f32 add), the points generated in the kernel.  The dense
+ *     calls take at most 2^30 points; the sparse call dims 2..65,536 per axis, 64-bit indices and at
+ *     most 2^30 bricks.
+ *  2. Values.  Every value used is the composed field at a lattice point, with nr_compose_sample's
+ *     bits for that point, value and owner, the frame being the owner context's.  A point's value
+ *     depends only on that point: the same bits for any workgroup size, grid, occupancy or lattice that
+ *     contains the point.  The field is a distance only near the parts: outside every part's bound it
+ *     is the nearest bound's distance, scale * (sqrtf(qq) - 1.19f), and at a bound's edge (qq = 1.45)
+ *     it is discontinuous -- a network's tanh inside, about 0.014 * scale outside.  A level iso above
+ *     0.014 * scale therefore shows the bound spheres, not the models.
+ *  3. Mesh.  nr_mesh_grid's mesh of those values at iso, bit for bit: vertices, numbering, triangles,
+ *     windings, the capacity and counting protocol (rule 5 there) and the NaN rules.  iso is any finite
+ *     value.
+ *  4. Sparse.  Rules 2 and 4-6 of nr_extract_mesh_sparse word for word, with "the composed field" in
+ *     the place of sceneSDF: the bricks, activity by band, one vertex per shared edge, keys, the fixed
+ *     but unspecified order, the capacities.  What the band proves is less than for one network: the
+ *     field's discontinuity at the bound edges is a step of up to about scale * (1 - 0.014), so a
+ *     band below that can cull a brick whose corners all lie outside a bound the surface lies within;
+ *     the default of the Python binding (the brick's diagonal) is sound only while bricks are small
+ *     against the parts.
+ *  5. Normals and part.  normals[v] = the normalised tetrahedral gradient of the composed field at
+ *     vertices[v] (epsilon 1e-5): nr_compose_trace_rays' hit normal in the same arithmetic.  part[v] =
+ *     the owner of the composed field at vertices[v], the value nr_compose_sample returns there.
+ *     Each needs vertices; either may be NULL.
+ *  6. Stats (may be NULL).  ray_steps = lattice points evaluated -- for the sparse call
+ *     nr_extract_mesh_sparse's sum, the brick-corner lattice plus the active bricks' point sets;
+ *     part_evals = (lattice point, part) pairs inside that part's bound over the sampling passes
+ *     (not the vertex pass), independent of the grouping; rays_hit = active bricks (sparse) or 0
+ *     (dense); rays_shaded = *nv; shade_evals = 4 * *nv with normals plus *nv with part; wave_evals
+ *     and wave_skips as elsewhere (they depend on the grouping), over all passes; iterations = 0;
+ *     launches (the zeroing of the statistics counts as one) and ms_total as elsewhere.
+ *  7. Errors.  Those of the composed calls and of the mesh calls, the message through nr_last_error
+ *     of the owner.  NR_E_INVALID: a NULL composition, origin, step, dims, nv or nt; nr_compose_sample_grid
+ *     with value and owner both NULL or a dim < 1; a dim < 2 (dense mesh) or outside 2..65,536
+ *     (sparse); more than 2^30 points (dense) or bricks (sparse); iso not finite; only one of
+ *     vertices / triangles given; normals, part or keys without vertices; brick not 4, 8 or 16; band
+ *     negative or NaN; more than 2^31 - 1 vertices.  NR_E_NOMEM: short capacities (nothing written),
+ *     or scratch that cannot be allocated.
+ *  8. Scratch.  The owner context's, the buffers nr_mesh_grid, nr_extract_mesh and
+ *     nr_extract_mesh_sparse use on it, kept until nr_destroy; the owner needs no network.  Dense: 8
+ *     bytes per lattice point (value, pass word) + 24 bytes per 256 points.  Sparse: per brick 4 bytes
+ *     + 4 bytes per point of the brick-corner lattice + 24 bytes per 256 bricks; per active brick 4
+ *     bytes + 8 bytes per active point ((B + 1)^3 rounded up to a multiple of 64: 128, 768 or 4,928)
+ *     + 24 bytes per 256 active points.  For loc = NR_HOST also staging of the results' size.  The
+ *     active-brick count is read on the host once, as in nr_extract_mesh_sparse.
+ * All launches run on the owner's stream; the count, scan, emit and classify passes are those of the
+ * single-network calls. */
+int nr_compose_sample_grid(nr_compose *c, const float origin[3], const float step[3], const int dims[3],
+                           float *value /*[nz][ny][nx] or NULL*/, int32_t *owner /*[nz][ny][nx] or NULL*/,
+                           int loc, nr_compose_stats *stats);
+int nr_compose_extract_mesh(nr_compose *c, const float origin[3], const float step[3], const int dims[3], float iso,
+                            float *vertices /*[v_cap][3]*/, float *normals /*[v_cap][3] or NULL*/,
+                            int32_t *part /*[v_cap] or NULL*/, long v_cap,
+                            int32_t *triangles /*[t_cap][3]*/, long t_cap, long *nv, long *nt, int loc,
+                            nr_compose_stats *stats);
+int nr_compose_extract_mesh_sparse(nr_compose *c, const float origin[3], const float step[3], const int dims[3],
+                                   float iso, int brick, float band,
+                                   float *vertices /*[v_cap][3]*/, float *normals /*[v_cap][3] or NULL*/,
+                                   int32_t *part /*[v_cap] or NULL*/, int64_t *keys /*[v_cap] or NULL*/, long v_cap,
+                                   int32_t *triangles /*[t_cap][3]*/, long t_cap,
+                                   long *nv, long *nt, long *active_bricks /*or NULL*/, int loc, nr_compose_stats *stats);
+
 /* One DenseLayer::forward (denseLayer.cu:229-278) on device buffers: layer l of the
  * loaded network applied to A [n][dims[l]] -> Z [n][dims[l+1]]. */
 int nr_layer_forward(nr_ctx *ctx, int layer, const float *A, float *Z, long n, int loc);
