@@ -48,6 +48,7 @@ EXPORTS = [
     "nr_compose_create", "nr_compose_destroy", "nr_compose_bound", "nr_compose_set_parts", "nr_compose_info",
     "nr_compose_sample", "nr_compose_trace_rays", "nr_compose_gbuffer", "nr_compose_render",
     "nr_compose_sample_grid", "nr_compose_extract_mesh", "nr_compose_extract_mesh_sparse",
+    "nr_compose_render_lit",
 ]
 # composed scenes (nr_compose_*): limits and part ops
 NR_COMPOSE_MAX_NETS, NR_COMPOSE_MAX_PARTS = 4, 16
@@ -263,6 +264,7 @@ def lib():
         "nr_compose_trace_rays": (I, [P, P, P, L64, I, P, P, P, P, P, P, I, ctypes.POINTER(NRComposeStats)]),
         "nr_compose_gbuffer": (I, [P, I, I, I, P, P, P, P, P, P, I, ctypes.POINTER(NRComposeStats)]),
         "nr_compose_render": (I, [P, P, I, I, I, P, I, ctypes.POINTER(NRComposeStats)]),
+        "nr_compose_render_lit": (I, [P, P, I, I, I, ctypes.POINTER(NRLight), P, P, P, P, I, ctypes.POINTER(NRComposeStats)]),
         "nr_compose_sample_grid": (I, [P, FP, FP, IP, P, P, I, ctypes.POINTER(NRComposeStats)]),
         "nr_compose_extract_mesh": (I, [P, FP, FP, IP, F, P, P, P, L64, P, L64, ctypes.POINTER(L64), ctypes.POINTER(L64), I,
                                         ctypes.POINTER(NRComposeStats)]),

@@ -1595,6 +1595,19 @@ int nr_render_aa(nr_ctx *c, uint32_t *out, int W, int H, int samples, int mode, 
 
 // ---- ambient occlusion and soft shadows (nr_light.hip) ----
 
+// The checks on the fields of a light, shared by nr_render_lit and nr_compose_render_lit.
+static int check_light(nr_ctx *c, const char *fn, const nr_light &l) {
+    const float lf[8] = {l.dir[0], l.dir[1], l.dir[2], l.shadow_bias, l.shadow_k, l.ao_step, l.ao_strength, l.ambient};
+    for (float v : lf)
+        if (!std::isfinite(v)) return set_err(c, NR_E_INVALID, "%s: a non-finite light field", fn);
+    if (l.dir[0] == 0.0f && l.dir[1] == 0.0f && l.dir[2] == 0.0f) return set_err(c, NR_E_INVALID, "%s: dir is zero", fn);
+    if (l.shadow_steps < 0) return set_err(c, NR_E_INVALID, "%s: shadow_steps < 0", fn);
+    if (l.shadow_k < 0.0f || l.ao_step < 0.0f || l.ao_strength < 0.0f)
+        return set_err(c, NR_E_INVALID, "%s: negative shadow_k, ao_step or ao_strength", fn);
+    if (l.ambient < 0.0f || l.ambient > 1.0f) return set_err(c, NR_E_INVALID, "%s: ambient outside 0..1", fn);
+    return NR_OK;
+}
+
 // Three launches on the context's stream: the geometry buffer (k_query<true>) into context scratch,
 // k_light_trace over its pixels (ao and shadow), k_light_resolve where a frame is wanted.  No
 // host read in between: the tracer's cursor runs over all pixels, not over a list of the hits.
@@ -1607,14 +1620,7 @@ int nr_render_lit(nr_ctx *c, uint32_t *out, int W, int H, int max_steps, const n
     if ((long)W * H > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_render_lit: bad size %dx%d", W, H);
     if (max_steps < 1) return set_err(c, NR_E_INVALID, "nr_render_lit: max_steps < 1");
     const nr_light &l = *light;
-    const float lf[8] = {l.dir[0], l.dir[1], l.dir[2], l.shadow_bias, l.shadow_k, l.ao_step, l.ao_strength, l.ambient};
-    for (float v : lf)
-        if (!std::isfinite(v)) return set_err(c, NR_E_INVALID, "nr_render_lit: a non-finite light field");
-    if (l.dir[0] == 0.0f && l.dir[1] == 0.0f && l.dir[2] == 0.0f) return set_err(c, NR_E_INVALID, "nr_render_lit: dir is zero");
-    if (l.shadow_steps < 0) return set_err(c, NR_E_INVALID, "nr_render_lit: shadow_steps < 0");
-    if (l.shadow_k < 0.0f || l.ao_step < 0.0f || l.ao_strength < 0.0f)
-        return set_err(c, NR_E_INVALID, "nr_render_lit: negative shadow_k, ao_step or ao_strength");
-    if (l.ambient < 0.0f || l.ambient > 1.0f) return set_err(c, NR_E_INVALID, "nr_render_lit: ambient outside 0..1");
+    if ((rc = check_light(c, "nr_render_lit", l)) != NR_OK) return rc;
     if (c->dims.empty()) return set_err(c, NR_E_STATE, "nr_render_lit: no network loaded");
     if (!c->fused)
         return set_err(c, NR_E_FORMAT, "nr_render_lit: needs a [3|4, 32, ..., 32, 1] network (no layered fallback)");
@@ -2426,6 +2432,16 @@ struct nr_compose {
     size_t cap_gbuf = 0;
     uint32_t *d_out = nullptr;
     size_t cap_out = 0;
+    // nr_compose_render_lit: the lighting launch's cursor and stats (as d_cs), its geometry buffer
+    // (status, position, normal: 28 B per pixel), ao and shadow where the caller gave no device
+    // buffer, and the staging of a host part and occluder
+    uint32_t *d_ls = nullptr;
+    float *d_lgbuf = nullptr;
+    size_t cap_lgbuf = 0;
+    float *d_lao = nullptr;
+    size_t cap_lao = 0;
+    int32_t *d_lown = nullptr;
+    size_t cap_lown = 0;
 };
 constexpr size_t COMPOSE_CS_BYTES = 128 + 7 * 8;
 
@@ -2569,6 +2585,7 @@ int nr_compose_destroy(nr_compose *cp) {
     (void)hipSetDevice(c->device);
     if (!(c->use_own && !c->own_stream)) (void)hipStreamSynchronize(c->stream);
     dfree(cp->d_packs); dfree(cp->d_cs); dfree(cp->d_io); dfree(cp->d_gbuf); dfree(cp->d_out);
+    dfree(cp->d_ls); dfree(cp->d_lgbuf); dfree(cp->d_lao); dfree(cp->d_lown);
     delete cp;
     return NR_OK;
 }
@@ -2739,6 +2756,148 @@ int nr_compose_render(nr_compose *cp, uint32_t *out, int W, int H, int max_steps
     if (max_steps < 1) return set_err(c, NR_E_INVALID, "nr_compose_render: max_steps < 1");
     return compose_rays(cp, "nr_compose_render", nullptr, nullptr, (long)W * H, W, H, max_steps, nullptr, nullptr, nullptr,
                         nullptr, nullptr, part, out, loc, stats);
+}
+
+// ---- ambient occlusion and shadows of a composed scene (nr_compose_light.hip) ----
+
+// The workgroup of a k_compose_light launch and its grid: compose_shape's choice with
+// compose_light_lds_bytes in the fit test, and 768 -> 512 -> 256 threads where the two per-wave
+// lists do not fit beside the packs.  false: not even four waves' lists fit.
+static bool compose_light_shape(const nr_compose *cp, size_t n, int &threads, int &grid) {
+    const nr_ctx *c = cp->owner;
+    const bool one = cp->npacks == 1;
+    int bpc = 1;
+    if (c->blocks_per_cu > 0 || one) {
+        threads = 256;
+    } else {
+        threads = 768;
+        while (threads > 256 && compose_light_lds_bytes(cp->A, threads) > NR_LDS_PER_CU) threads -= 256;
+    }
+    const int bytes = compose_light_lds_bytes(cp->A, threads);
+    if (bytes > NR_LDS_PER_CU) return false;
+    if (c->blocks_per_cu > 0 || one) bpc = std::min(c->blocks_per_cu > 0 ? c->blocks_per_cu : 2, std::max(1, NR_LDS_PER_CU / bytes));
+    grid = (int)std::max<size_t>(1, std::min<size_t>((n + threads - 1) / threads, (size_t)num_cus(c->device) * bpc));
+    return true;
+}
+
+// Launches on the owner's stream: the geometry buffer (k_compose<true>) into the composition's
+// scratch, k_compose_light over its pixels (ao, shadow, occluder), k_light_resolve where a frame is
+// wanted.  No host read in between.
+int nr_compose_render_lit(nr_compose *cp, uint32_t *out, int W, int H, int max_steps, const nr_light *light, float *ao,
+                          float *shadow, int32_t *part, int32_t *occluder, int loc, nr_compose_stats *stats) {
+    if (!cp) return set_err(nullptr, NR_E_INVALID, "nr_compose_render_lit: composition is NULL");
+    nr_ctx *c = cp->owner;
+    if (!light) return set_err(c, NR_E_INVALID, "nr_compose_render_lit: light is NULL");
+    if (!out && !ao && !shadow) return set_err(c, NR_E_INVALID, "nr_compose_render_lit: no output wanted");
+    if (W < 1 || H < 1 || (long)W * H > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_compose_render_lit: bad size %dx%d", W, H);
+    if (max_steps < 1) return set_err(c, NR_E_INVALID, "nr_compose_render_lit: max_steps < 1");
+    const nr_light &l = *light;
+    int rc;
+    if ((rc = check_light(c, "nr_compose_render_lit", l)) != NR_OK) return rc;
+    if (out && c->color_type == NR_COLOR_MATCAP && !c->d_matcap)
+        return set_err(c, NR_E_STATE, "nr_compose_render_lit: matcap colouring without a matcap");
+    const size_t N = (size_t)W * H;
+    int threads, grid, lthreads, lgrid;
+    compose_shape(cp, N, threads, grid);
+    if (!compose_light_shape(cp, N, lthreads, lgrid))
+        return set_err(c, NR_E_INVALID, "nr_compose_render_lit: the packs and the per-wave lists need %d bytes of LDS (limit %d)",
+                       compose_light_lds_bytes(cp->A, 256), NR_LDS_PER_CU);
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const bool host = loc != NR_DEVICE;
+    // ---- scratch: the geometry buffer, the values without a device buffer of the caller's, the frame's staging
+    if (!cp->d_ls) HIPCHK(c, hipMalloc(&cp->d_ls, COMPOSE_CS_BYTES));
+    if ((rc = ensure_buf(c, cp->d_lgbuf, cp->cap_lgbuf, 7 * N)) != NR_OK) return rc;
+    float *d_ao = host ? nullptr : ao, *d_shadow = host ? nullptr : shadow;
+    if ((rc = ensure_buf(c, cp->d_lao, cp->cap_lao, (d_ao ? 0 : N) + (d_shadow ? 0 : N))) != NR_OK) return rc;
+    if (!d_shadow) d_shadow = cp->d_lao;
+    if (!d_ao) d_ao = d_shadow == cp->d_lao ? cp->d_lao + N : cp->d_lao;
+    int32_t *d_part = part, *d_occ = occluder;
+    if (host) {
+        if ((rc = ensure_buf(c, cp->d_lown, cp->cap_lown, (part ? N : 0) + (occluder ? N : 0))) != NR_OK) return rc;
+        if (part) d_part = cp->d_lown;
+        if (occluder) d_occ = cp->d_lown + (part ? N : 0);
+    }
+    uint32_t *dout = out;
+    if (out && host) {
+        if ((rc = ensure_buf(c, cp->d_out, cp->cap_out, N)) != NR_OK) return rc;
+        dout = cp->d_out;
+    }
+    // ---- pass A: the geometry buffer
+    ComposeArgs Q = cp->A;
+    Q.n = (long)N; Q.W = W; Q.H = H;
+    Q.inv_w = 1.0 / (double)W;
+    Q.rcp_w = pow2_rcp(W); Q.rcp_h = pow2_rcp(H);
+    memcpy(Q.inv_view, c->inv_view, sizeof Q.inv_view);
+    Q.max_steps = max_steps; Q.frame = c->frame;
+    Q.cursor = cp->d_cs;
+    Q.stats = reinterpret_cast<unsigned long long *>(cp->d_cs + 32);
+    Q.status = reinterpret_cast<int32_t *>(cp->d_lgbuf);
+    Q.position = cp->d_lgbuf + N;
+    Q.normal = cp->d_lgbuf + 4 * N;
+    Q.part = d_part;
+    // ---- pass B: ao, shadow and occluder of every pixel
+    ComposeArgs B = cp->A;
+    B.n = (long)N; B.frame = c->frame;
+    B.cursor = cp->d_ls;
+    B.stats = reinterpret_cast<unsigned long long *>(cp->d_ls + 32);
+    ComposeLightArgs X{};
+    X.status = Q.status; X.position = Q.position; X.normal = Q.normal;
+    for (int a = 0; a < 3; ++a) X.dir[a] = l.dir[a];
+    X.shadow_steps = l.shadow_steps; X.shadow_bias = l.shadow_bias; X.shadow_k = l.shadow_k;
+    X.ao_step = l.ao_step; X.ao_strength = l.ao_strength;
+    X.ao = d_ao; X.shadow = d_shadow; X.occluder = d_occ;
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, hipMemsetAsync(cp->d_cs, 0, COMPOSE_CS_BYTES, s));
+    HIPCHK(c, launch_compose(Q, grid, threads, s));
+    HIPCHK(c, hipMemsetAsync(cp->d_ls, 0, COMPOSE_CS_BYTES, s));
+    HIPCHK(c, launch_compose_light(B, X, lgrid, lthreads, s));
+    int launches = 4;
+    if (out) {
+        // ---- pass C: the base colour times the light (k_light_resolve reads these fields of LightArgs)
+        LightArgs R{};
+        R.n = (long)N;
+        R.status = Q.status; R.normal = Q.normal;
+        for (int a = 0; a < 3; ++a) R.dir[a] = l.dir[a];
+        R.ambient = l.ambient;
+        R.ao = d_ao; R.shadow = d_shadow;
+        RenderArgs A = render_args(c, W, H, H, H, 1, 0, max_steps);
+        A.out = dout;
+        A.frame = c->frame;
+        memcpy(A.inv_view, c->inv_view, sizeof A.inv_view);
+        memcpy(A.normal, c->normal, sizeof A.normal);
+        HIPCHK(c, launch_light_resolve(A, R, s));
+        launches += 1;
+    }
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (host) {
+        if (out) HIPCHK(c, hipMemcpyAsync(out, dout, N * 4, hipMemcpyDeviceToHost, s));
+        if (ao) HIPCHK(c, hipMemcpyAsync(ao, d_ao, N * 4, hipMemcpyDeviceToHost, s));
+        if (shadow) HIPCHK(c, hipMemcpyAsync(shadow, d_shadow, N * 4, hipMemcpyDeviceToHost, s));
+        if (part) HIPCHK(c, hipMemcpyAsync(part, d_part, N * 4, hipMemcpyDeviceToHost, s));
+        if (occluder) HIPCHK(c, hipMemcpyAsync(occluder, d_occ, N * 4, hipMemcpyDeviceToHost, s));
+    }
+    unsigned long long hs[7], hl[7];
+    if (stats) {
+        HIPCHK(c, hipMemcpyAsync(hs, Q.stats, sizeof hs, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(hl, B.stats, sizeof hl, hipMemcpyDeviceToHost, s));
+    }
+    float ms = 0.0f;
+    rc = end_timed(c, stats != nullptr, loc, s, &ms);
+    if (rc != NR_OK || !stats) return rc;
+    nr_compose_stats st{};
+    st.ray_steps = hs[0] + hl[0];
+    st.rays_hit = hs[1];
+    st.rays_shaded = hs[3];
+    st.shade_evals = (l.ao_strength > 0.0f ? 8ull : 4ull) * hs[3];
+    st.part_evals = hs[4] + hl[4];
+    st.wave_evals = hs[5] + hl[5];
+    st.wave_skips = hs[6] + hl[6];
+    st.iterations = (int32_t)std::max(hs[2], hl[2]);
+    st.launches = launches;
+    st.ms_total = ms;
+    *stats = st;
+    return NR_OK;
 }
 
 int nr_compose_sample(nr_compose *cp, const float *points, long n, float *value, int32_t *owner, int loc,

@@ -26,21 +26,6 @@ constexpr int NR_COMPOSE_REFILL_MIN = 4;
 constexpr int CSTASH = 80;
 static_assert(16 - 1 + 64 <= CSTASH, "the per-wave list of converged rays");
 
-// intersect_bounding (nr_device.h) against the sphere (c, r): the same expressions on Q = o - c and r2 = r * r
-__device__ __forceinline__ bool compose_intersect(F3 o, F3 d, const ComposeArgs &C, float &tnear, float &tfar) {
-    const F3 Qv = mk3(o.x - C.center[0], o.y - C.center[1], o.z - C.center[2]);
-    const float a = dot3(d, d);
-    const float b = 2.0f * dot3(Qv, d);
-    const float cc = dot3(Qv, Qv) - C.r2;
-    const float disc = b * b - 4 * a * cc;
-    if (!(disc > 0)) return false;
-    const float sq = sqrtf(disc);
-    const float a2 = 2.0f * a;
-    tnear = (-b - sq) / a2;
-    tfar = (-b + sq) / a2;
-    return true;
-}
-
 // k_compose<true>'s copy of the view in LDS
 struct ComposeView {
     float V[12];

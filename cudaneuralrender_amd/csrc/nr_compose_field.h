@@ -1,6 +1,7 @@
 // nr_compose_field.h -- the composed field as device functions, shared by the tracer and the point
-// sampler (nr_compose.hip) and by the lattice, brick and vertex kernels (nr_compose_mesh.hip), as
-// nr_grad.h is shared by nr_grad.hip and nr_project.hip: one definition, the same bits everywhere.
+// sampler (nr_compose.hip), by the lattice, brick and vertex kernels (nr_compose_mesh.hip) and by the
+// lighting tracer (nr_compose_light.hip), as nr_grad.h is shared by nr_grad.hip and nr_project.hip:
+// one definition, the same bits everywhere.
 #pragma once
 #include "nr_mlp16.h"
 
@@ -74,6 +75,21 @@ __device__ __forceinline__ F3 compose_tet_term(const ComposeArgs &C, const float
     const F3 pq = add3(sp, mul3s(tp, NORMAL_EPSILON));
     int own;
     return mul3s(tp, compose_field(C, lds, fr, pq, live, own, cnt));
+}
+
+// intersect_bounding (nr_device.h) against the sphere (c, r): the same expressions on Q = o - c and r2 = r * r
+__device__ __forceinline__ bool compose_intersect(F3 o, F3 d, const ComposeArgs &C, float &tnear, float &tfar) {
+    const F3 Qv = mk3(o.x - C.center[0], o.y - C.center[1], o.z - C.center[2]);
+    const float a = dot3(d, d);
+    const float b = 2.0f * dot3(Qv, d);
+    const float cc = dot3(Qv, Qv) - C.r2;
+    const float disc = b * b - 4 * a * cc;
+    if (!(disc > 0)) return false;
+    const float sq = sqrtf(disc);
+    const float a2 = 2.0f * a;
+    tnear = (-b - sq) / a2;
+    tfar = (-b + sq) / a2;
+    return true;
 }
 
 // the packs into dynamic LDS, block-wide 16-byte copies

@@ -329,6 +329,24 @@ hipError_t launch_compose_sample(const ComposeArgs &C, int grid, hipStream_t st)
 // colours the HIT pixels of a W x H geometry buffer (A: W, H, out, view, colouring), 0 elsewhere
 hipError_t launch_compose_color(const RenderArgs &A, const int32_t *status, const float *normal, hipStream_t st);
 
+// Lighting of a composed scene (nr_compose_light.hip; nr_compose_render_lit): the W x H geometry buffer
+// k_compose<true> left, the light, and one ao, one shadow and one occluder value per pixel.  The
+// ComposeArgs of the launch carry the packs, nets, parts, the bound, n = W H, frame, cursor and stats
+// ([0] shadow-ray steps, [2] the longest shadow ray's, [4] in-bound (marching shadow ray, part) pairs,
+// [5] wave evaluations issued, [6] skipped).
+struct ComposeLightArgs {
+    const int32_t *status;        // [n] NR_RAY_*
+    const float *position, *normal;  // [n][3], of the hits
+    float dir[3];                 // nr_light, field by field
+    int shadow_steps;
+    float shadow_bias, shadow_k, ao_step, ao_strength;
+    float *ao, *shadow;           // [n], both always written
+    int32_t *occluder;            // [n] or NULL: the owner at the converging step of a shadow ray that ends HIT, else -1
+};
+// dynamic LDS of a k_compose_light workgroup of `threads` threads: the packs, then two lists of hit pixels per wave
+int compose_light_lds_bytes(const ComposeArgs &C, int threads);
+hipError_t launch_compose_light(const ComposeArgs &C, const ComposeLightArgs &X, int grid, int threads, hipStream_t st);  // threads: 256, 512 or 768
+
 // Composed-scene lattices and meshes (nr_compose_mesh.hip; nr_compose_sample_grid,
 // nr_compose_extract_mesh, nr_compose_extract_mesh_sparse).  The ComposeArgs of these launches carry
 // the packs, nets, parts, frame and stats ([4] in-bound (lattice point, part) pairs of the sampling

@@ -1021,6 +1021,44 @@ class Composition:
         res = (img,) + ((part,) if with_part else ()) + ((st.as_dict(),) if with_stats else ())
         return res if len(res) > 1 else img
 
+    # -- ambient occlusion and shadows cast between the parts
+    def render_lit(self, W, H, light_dir, shadow_steps=64, shadow_bias=0.01, shadow_k=8.0, ao_step=0.02,
+                   ao_strength=2.0, ambient=0.3, max_steps=6000, buffers=False, with_part=False, with_occluder=False,
+                   with_stats=False):
+        """nr_compose_render_lit: render()'s frame lit by one directional light as Renderer.render_lit
+        lights a single network, with the occlusion and the shadow rays taken through the composed
+        field: a part shades the others, a cut-out lies in the dark.  Returns the (H, W) uint32 image;
+        buffers=True adds the (H, W) float32 ao and shadow, with_part the (H, W) int32 owner map,
+        with_occluder the (H, W) int32 map of the part that blocked each pixel's light (-1: none),
+        with_stats the stats dict, in this order."""
+        out = np.zeros((H, W), np.uint32)
+        ao = np.zeros((H, W), np.float32) if buffers else None
+        sh = np.zeros((H, W), np.float32) if buffers else None
+        part = np.zeros((H, W), np.int32) if with_part else None
+        occ = np.zeros((H, W), np.int32) if with_occluder else None
+        lt = Renderer._light(light_dir, shadow_steps, shadow_bias, shadow_k, ao_step, ao_strength, ambient)
+        st = NRComposeStats()
+        self._chk(self._L.nr_compose_render_lit(self._c, out.ctypes.data, int(W), int(H), int(max_steps), ctypes.byref(lt),
+                                                *[a.ctypes.data if a is not None else None for a in (ao, sh, part, occ)],
+                                                NR_HOST, ctypes.byref(st) if with_stats else None))
+        res = (out,) + ((ao, sh) if buffers else ()) + ((part,) if with_part else ()) + ((occ,) if with_occluder else ())
+        if with_stats:
+            res += (st.as_dict(),)
+        return res if len(res) > 1 else out
+
+    def render_lit_device(self, out_ptr, W, H, light_dir, shadow_steps=64, shadow_bias=0.01, shadow_k=8.0, ao_step=0.02,
+                          ao_strength=2.0, ambient=0.3, max_steps=6000, ao_ptr=None, shadow_ptr=None, part_ptr=None,
+                          occluder_ptr=None, with_stats=False):
+        """nr_compose_render_lit into device buffers (W * H uint32 for the frame, float32 for ao and
+        shadow, int32 for part and occluder; None = that output is not wanted, but not all of out, ao
+        and shadow), on the owner's stream.  Without stats it returns without waiting."""
+        vp = [ctypes.c_void_p(p) if p else None for p in (out_ptr, ao_ptr, shadow_ptr, part_ptr, occluder_ptr)]
+        lt = Renderer._light(light_dir, shadow_steps, shadow_bias, shadow_k, ao_step, ao_strength, ambient)
+        st = NRComposeStats()
+        self._chk(self._L.nr_compose_render_lit(self._c, vp[0], int(W), int(H), int(max_steps), ctypes.byref(lt), *vp[1:],
+                                                NR_DEVICE, ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
     # -- lattice sampling / isosurface extraction of the composed field
     def sample_grid(self, origin, step, dims, owner=False, with_stats=False):
         """nr_compose_sample_grid: the composed field at the lattice points origin + (i, j, k) * step,

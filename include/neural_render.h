@@ -689,6 +689,53 @@ int nr_compose_gbuffer(nr_compose *c, int W, int H, int max_steps, int32_t *stat
 int nr_compose_render(nr_compose *c, uint32_t *out /*W*H*/, int W, int H, int max_steps, int32_t *part /*W*H or NULL*/,
                       int loc, nr_compose_stats *stats);
 
+/* ---- composed scenes: ambient occlusion and shadows cast between parts ------------- */
+/* (one new symbol: NR_ABI_VERSION stays 3; nr_light, nr_stats and nr_compose_stats are unchanged)
+ *
+ * nr_render_lit for a composition: the frame of nr_compose_render lit by one directional light, the
+ * occlusion and the shadow taken from the composed field, so that a part darkens the others and a
+ * cut-out lies in the shadow of what surrounds it -- the geometry buffer, one persistent lighting
+ * launch over the composed field, one compositing launch; no host round trip.  Rules 1-9 of
+ * nr_render_lit hold word for word with these differences:
+ *  1. G is what nr_compose_gbuffer(W, H, max_steps) returns for the owner's view and frame (status,
+ *     position, normal, part); base is nr_compose_render's W x H frame (the owner's colouring and
+ *     matcap).
+ *  2. The field.  Wherever nr_render_lit evaluates sceneSDF(x, mlp(x)) -- s_q of rule 3, tstep of
+ *     rule 4 -- this call evaluates the composed field at x (above): always NR_SCENE_TANH's value
+ *     per part, the owner's frame number for 4-input networks; nr_set_scene on the owner is not read.
+ *  3. The shadow ray.  o = p + n * shadow_bias, d = L is marched by the composed ray rule (Rays,
+ *     above) with shadow_steps in the place of max_steps: the entry on the world bound, tnear =
+ *     max(tnear, 0), tfar reduced by tnear, then per iteration tstep = field(p), rule 4's running
+ *     minimum (dist = tnear + travel; if dist > 0, r = shadow_k * tstep / dist, res = r where r <
+ *     res), then the composed step and end tests.  MISS gives 1.0f; ESCAPED shadow_k > 0 ? sat(res)
+ *     : 1.0f; HIT and LIMIT 0.0f.
+ *  4. occluder[i] = the part that blocked the light: the owner at the converging step of pixel i's
+ *     shadow ray where that ray ends HIT, -1 for every other pixel (not a HIT pixel, no ray marched,
+ *     a ray that ends MISS, ESCAPED or LIMIT).  part[i] is nr_compose_gbuffer's.
+ *  5. With ao_strength = 0, shadow_steps = 0 and ambient = 1, out is nr_compose_render's frame, bit
+ *     for bit.
+ *  6. Settings.  The outputs depend only on the inputs: the same bits for any workgroup size, grid,
+ *     occupancy (nr_set_occupancy on the owner) or order in which the pixels are dealt.
+ *  7. Outputs.  out, ao, shadow, part and occluder (W H values each, index y * W + x) may each be
+ *     NULL, but not all of out, ao and shadow; loc = NR_HOST or NR_DEVICE for all of them.  stats
+ *     (may be NULL): ray_steps = the geometry buffer's plus the sum of the shadow rays' steps;
+ *     rays_hit and rays_shaded the geometry buffer's; shade_evals = 4 per HIT, plus 4 per HIT with
+ *     ambient occlusion on; part_evals = the (marching ray, part) pairs in bound of the primary and
+ *     of the shadow rays; wave_evals and wave_skips summed over both launches (the occlusion passes
+ *     count there, as the normal passes do); iterations = the larger of the primary and the shadow
+ *     rays' longest; launches and ms_total as elsewhere.
+ *  8. Errors.  NR_E_INVALID: c or light NULL, out, ao and shadow all NULL, W or H < 1, W H > 2^30,
+ *     max_steps < 1, and nr_render_lit's checks of the light fields.  NR_E_STATE: matcap colouring
+ *     without a matcap when out is wanted.
+ *  9. Scratch.  The composition owns it and keeps it until nr_compose_destroy: 28 bytes per pixel of
+ *     geometry buffer, 8 bytes per pixel (ao, shadow) where the caller gave none or gave host
+ *     pointers (4 for one of the two), and for loc = NR_HOST 4 bytes per pixel for each of out, part
+ *     and occluder that is wanted. */
+int nr_compose_render_lit(nr_compose *c, uint32_t *out /*W*H or NULL*/, int W, int H, int max_steps,
+                          const nr_light *light, float *ao /*W*H or NULL*/, float *shadow /*W*H or NULL*/,
+                          int32_t *part /*W*H or NULL*/, int32_t *occluder /*W*H or NULL*/, int loc,
+                          nr_compose_stats *stats);
+
 /* ---- composed scenes: lattice sampling and mesh extraction ------------------------- */
 /* (new symbols only: NR_ABI_VERSION stays 3, nr_stats and nr_compose_stats are unchanged)
  *
