@@ -15,6 +15,8 @@ from .renderer import (NR_COLOR_FACING, NR_COLOR_MATCAP, Group, Renderer, assemb
                        group_layout)
 from ._lib import NR_COMPOSE_MAX_NETS, NR_COMPOSE_MAX_PARTS, NR_PART_OP, NRComposeStats, NRPart  # noqa: F401
 from .renderer import Composition, compose_bound, make_parts  # noqa: F401
+from ._lib import NRFitOpts  # noqa: F401
+from .renderer import Fit  # noqa: F401
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_DIR = os.path.dirname(PKG_DIR)

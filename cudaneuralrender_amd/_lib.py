@@ -49,6 +49,7 @@ EXPORTS = [
     "nr_compose_sample", "nr_compose_trace_rays", "nr_compose_gbuffer", "nr_compose_render",
     "nr_compose_sample_grid", "nr_compose_extract_mesh", "nr_compose_extract_mesh_sparse",
     "nr_compose_render_lit",
+    "nr_fit_create", "nr_fit_destroy", "nr_fit_num_params", "nr_fit_gradient", "nr_fit_run", "nr_fit_weights",
 ]
 # composed scenes (nr_compose_*): limits and part ops
 NR_COMPOSE_MAX_NETS, NR_COMPOSE_MAX_PARTS = 4, 16
@@ -102,6 +103,19 @@ class NRProjectOpts(ctypes.Structure):
         ("tol", ctypes.c_float),
         ("max_step", ctypes.c_float),
         ("max_iters", ctypes.c_int),
+    ]
+
+
+class NRFitOpts(ctypes.Structure):
+    """nr_fit_opts: Adam's constants, the residual clamp, the partial sums and the grid of nr_fit_*."""
+    _fields_ = [
+        ("lr", ctypes.c_float),
+        ("beta1", ctypes.c_float),
+        ("beta2", ctypes.c_float),
+        ("eps", ctypes.c_float),
+        ("clamp", ctypes.c_float),
+        ("partials", ctypes.c_int),
+        ("grid", ctypes.c_int),
     ]
 
 
@@ -270,6 +284,12 @@ def lib():
                                         ctypes.POINTER(NRComposeStats)]),
         "nr_compose_extract_mesh_sparse": (I, [P, FP, FP, IP, F, I, F, P, P, P, P, L64, P, L64, ctypes.POINTER(L64),
                                                ctypes.POINTER(L64), ctypes.POINTER(L64), I, ctypes.POINTER(NRComposeStats)]),
+        "nr_fit_create": (I, [P, I, IP, ctypes.POINTER(FP), ctypes.POINTER(FP), ctypes.POINTER(NRFitOpts), ctypes.POINTER(P)]),
+        "nr_fit_destroy": (I, [P]),
+        "nr_fit_num_params": (I, [P, ctypes.POINTER(L64)]),
+        "nr_fit_gradient": (I, [P, P, P, L64, P, P, P, I]),
+        "nr_fit_run": (I, [P, P, P, L64, L64, P, I, ctypes.POINTER(NRStats)]),
+        "nr_fit_weights": (I, [P, P, ctypes.POINTER(L64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -65,6 +65,29 @@ NR_HD constexpr inline int gb_l0(int nh) { return nh * 1024; }
 NR_HD constexpr inline int gb_last(int nh) { return gb_l0(nh) + 512; }
 NR_HD constexpr inline int gb_floats(int nh) { return gb_last(nh) + 32; }
 
+// The fit pack (nr_fit.hip; nr_fit_*): what k_fit_grad stages in LDS and k_fit_update rewrites on the
+// device after every step, in floats, raw weights.
+//   forward, pk_floats(nh) floats in the PK_* layout above, except that every ReLU layer keeps unit
+//   4k + g in register k of lane group g (the last one too) and the final layer is
+//   [unit 32] in natural order, bias [1] (+3 pad): its chain runs in the point's lane over staged
+//   activations;
+//   backward, at fit_bwd(nh): hidden layer j's transposed A operand at j * 1024, as the backward
+//   pack's.  (No transposed K_0 and no copy of the last kernel: the weight gradients need d_0 but
+//   not d value / d input, and the last kernel is read from the forward part.)
+// Flat parameter order (nr_fit_gradient's grad, nr_fit_weights' params): K_0 [3][32], B_0 [32],
+// K_l [32][32], B_l [32] for l = 1..nh, K_last [32], B_last [1].
+NR_HD constexpr inline int fit_bwd(int nh) { return pk_floats(nh); }
+NR_HD constexpr inline int fit_pack_floats(int nh) { return pk_floats(nh) + nh * 1024; }
+NR_HD constexpr inline int fit_off_k(int l) { return l == 0 ? 0 : 128 + (l - 1) * 1056; }  // l = 0 .. nh + 1
+NR_HD constexpr inline int fit_off_b(int l) { return l == 0 ? 96 : fit_off_k(l) + 1024; }  // l = 0 .. nh
+NR_HD constexpr inline int fit_params(int nh) { return fit_off_k(nh + 1) + 33; }
+// per-wave LDS of k_fit_grad, in floats: the nh + 1 ReLU layers' activations and one layer's deltas
+// as [unit 32][point 16], the inputs [4][16] (row 3: ones), the residuals e and g [2][16]
+NR_HD constexpr inline int fit_wave_floats(int nh) { return (nh + 2) * 512 + 64 + 32; }
+constexpr int FIT_WAVES = 4;
+constexpr int FIT_CHUNKS = 16;  // the totals' two-level order (include/neural_render.h, nr_fit_*)
+constexpr int FIT_PARTIALS_DEFAULT = 1024;
+
 // Low-precision (bf16/fp16) pack for the 32-point-tile MLP (nr_mlp16.h, mlp32_lowp):
 // v_mfma_f32_32x32x16_{bf16,f16}, lane l = (row / point r = l & 31, half h = l >> 5).
 // 16-bit elements (a_ops):

@@ -266,6 +266,28 @@ struct GradArgs {
     int gb_bytes;
 };
 
+// Fitting (nr_fit.hip; nr_fit_*).  k_fit_grad: the weight gradients' partial sums of n points;
+// k_fit_update: their totals, then the gradient written out, or Adam and the packs rewritten.
+struct FitArgs {
+    const float *X, *Y;           // [n][3], [n]
+    long n;                       // 1 .. 2^30
+    const float *pack;            // the fit pack (nr_internal.h fit_pack_floats)
+    float *partial;               // [S][P + 1]: partial s's sums in flat parameter order, then SS
+    float *value;                 // [n] or NULL
+    float clamp;                  // > 0: the clamped residual
+    int S, nh;
+};
+enum { FIT_MODE_GRADIENT = 0, FIT_MODE_ADAM = 1, FIT_MODE_PACK = 2 };
+struct FitUpdArgs {
+    const float *partial;         // as FitArgs
+    int S, nh, mode;
+    float inv_n;
+    float *theta, *m, *v;         // [P] master weights and Adam's moments
+    float *pack;                  // the fit pack (ADAM, PACK: rewritten from theta)
+    float a_t, beta1, beta2, omb1, omb2, eps;
+    float *grad, *loss;           // GRADIENT: [P] or NULL; GRADIENT, ADAM: [1] or NULL
+};
+
 // Projection onto a level set (nr_project.hip k_project; nr_project_points): every point writes its
 // slot of the outputs that are not NULL.
 struct ProjArgs {
@@ -373,6 +395,9 @@ hipError_t launch_compose_sp_sample(const ComposeArgs &C, const SparseArgs &A, i
 int dense_lds_bytes(int in, int out);
 int grad_lds_bytes(const MlpArgs &M, const GradArgs &G);  // one k_grad workgroup's dynamic LDS
 hipError_t launch_grad(const GradArgs &G, const MlpArgs &M, int grid, hipStream_t st);  // 4-wave workgroups
+int fit_lds_bytes(int nh);  // one k_fit_grad workgroup's dynamic LDS
+hipError_t launch_fit_grad(const FitArgs &F, int grid, hipStream_t st);  // FIT_WAVES-wave workgroups
+hipError_t launch_fit_update(const FitUpdArgs &U, hipStream_t st);
 int project_lds_bytes(const MlpArgs &M, const ProjArgs &P);  // one k_project workgroup's dynamic LDS
 hipError_t launch_project(const ProjArgs &P, const MlpArgs &M, int grid, hipStream_t st);  // 4-wave workgroups
 hipError_t launch_grid(const GridArgs &G, const MlpArgs &M, int grid, hipStream_t st);

@@ -12,7 +12,7 @@ import numpy as np
 from ._lib import (NR_AA_CONTRAST_DEFAULT, NR_AA_MODE, NR_COLOR_FACING, NR_COLOR_MATCAP, NR_DEVICE, NR_GROUP_ASYNC,
                    NR_GROUP_COPY, NR_HOST, NR_PRECISION, NR_SCENE, NR_SCHEDULE, NRFrame, NRKernelProf, NRLight, NRProjectOpts,
                    NRStats, check, lib)
-from ._lib import NR_PART_OP, NRComposeStats, NRPart
+from ._lib import NR_PART_OP, NRComposeStats, NRFitOpts, NRPart
 
 _FP = ctypes.POINTER(ctypes.c_float)
 
@@ -1180,3 +1180,117 @@ class Composition:
             ctypes.byref(st) if with_stats else None))
         res = (nv.value, nt.value, na.value)
         return res + (st.as_dict(),) if with_stats else res
+
+
+class Fit:
+    """nr_fit: a [3, 32, ..., 32, 1] network trained on the device -- the weight gradients of the plain
+    or clamped L2 loss and Adam, bit for bit the arithmetic written in include/neural_render.h.
+    `renderer` supplies the device and the stream (it needs no network); the initial kernels and
+    biases are the caller's, in load_mlp's layout.  Close the fit before its renderer."""
+
+    def __init__(self, renderer, dims, kernels, biases, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, clamp=0.0,
+                 partials=0, grid=0):
+        self._L = lib()
+        self.owner = renderer
+        self._f = ctypes.c_void_p()
+        self.dims = [int(d) for d in dims]
+        nl = len(kernels)
+        d = (ctypes.c_int * (nl + 1))(*self.dims)
+        ks = [np.ascontiguousarray(k, np.float32) for k in kernels]
+        bs = [np.ascontiguousarray(b, np.float32) for b in biases]
+        kp = (_FP * nl)(*[_fptr(k) for k in ks])
+        bp = (_FP * nl)(*[_fptr(b) for b in bs])
+        opts = NRFitOpts(lr, beta1, beta2, eps, clamp, int(partials), int(grid))
+        renderer._chk(self._L.nr_fit_create(renderer._ctx, nl, d, kp, bp, ctypes.byref(opts), ctypes.byref(self._f)))
+        cnt = ctypes.c_long(0)
+        self._chk(self._L.nr_fit_num_params(self._f, ctypes.byref(cnt)))
+        self.num_params = cnt.value
+
+    def close(self):
+        if self._f:
+            # (the C object reaches through its owner: after an owner closed first it is left alone)
+            if self.owner._ctx:
+                self._L.nr_fit_destroy(self._f)
+            self._f = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _chk(self, rc):
+        return check(rc, self.owner._ctx)
+
+    def _split(self, flat):
+        K, B, q = [], [], 0
+        for i, o in zip(self.dims[:-1], self.dims[1:]):
+            K.append(flat[q:q + i * o].reshape(i, o).copy()); q += i * o
+            B.append(flat[q:q + o].copy()); q += o
+        return K, B
+
+    @staticmethod
+    def _xy(X, Y):
+        X = np.ascontiguousarray(X, np.float32)
+        Y = np.ascontiguousarray(Y, np.float32).reshape(-1)
+        if X.ndim != 2 or X.shape[1] != 3 or len(Y) != len(X):
+            raise ValueError(f"X must be [n, 3] and Y [n], got {X.shape} and {Y.shape}")
+        return X, Y
+
+    def gradient(self, X, Y, value=False):
+        """nr_fit_gradient on host arrays: {"loss", "grad": (kernels, biases)[, "value"]}; the weights stay."""
+        X, Y = self._xy(X, Y)
+        n = len(X)
+        loss = np.zeros(1, np.float32)
+        flat = np.zeros(self.num_params, np.float32)
+        val = np.zeros(n, np.float32) if value else None
+        self._chk(self._L.nr_fit_gradient(self._f, X.ctypes.data, Y.ctypes.data, n, loss.ctypes.data, flat.ctypes.data,
+                                          val.ctypes.data if value else None, NR_HOST))
+        out = {"loss": loss[0], "grad": self._split(flat), "flat": flat}
+        if value:
+            out["value"] = val
+        return out
+
+    def gradient_device(self, x_ptr, y_ptr, n, loss_ptr=None, grad_ptr=None, value_ptr=None):
+        """nr_fit_gradient on device buffers (float32 X [n, 3], Y [n], loss [1], grad [P], value [n]);
+        runs on the renderer's stream and returns without waiting."""
+        vp = [ctypes.c_void_p(p) if p else None for p in (x_ptr, y_ptr, loss_ptr, grad_ptr, value_ptr)]
+        self._chk(self._L.nr_fit_gradient(self._f, vp[0], vp[1], int(n), vp[2], vp[3], vp[4], NR_DEVICE))
+
+    def run(self, X, Y, batch, with_stats=False):
+        """nr_fit_run on host arrays: len(X) / batch Adam steps; returns each step's loss before its update."""
+        X, Y = self._xy(X, Y)
+        n = len(X)
+        loss = np.zeros(max(n // max(int(batch), 1), 1), np.float32)
+        st = NRStats()
+        self._chk(self._L.nr_fit_run(self._f, X.ctypes.data, Y.ctypes.data, n, int(batch), loss.ctypes.data, NR_HOST,
+                                     ctypes.byref(st) if with_stats else None))
+        return (loss, st.as_dict()) if with_stats else loss
+
+    def run_device(self, x_ptr, y_ptr, n, batch, loss_ptr=None, with_stats=False):
+        """nr_fit_run on device buffers (float32 X [n, 3], Y [n], loss [n / batch] or None): enqueues
+        the steps on the renderer's stream and, without stats, returns without waiting."""
+        st = NRStats()
+        self._chk(self._L.nr_fit_run(self._f, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), int(n), int(batch),
+                                     ctypes.c_void_p(loss_ptr) if loss_ptr else None, NR_DEVICE,
+                                     ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
+    def weights(self):
+        """(dims, kernels, biases, step): the master weights and the steps taken so far."""
+        flat = np.zeros(self.num_params, np.float32)
+        step = ctypes.c_long(0)
+        self._chk(self._L.nr_fit_weights(self._f, flat.ctypes.data, ctypes.byref(step)))
+        K, B = self._split(flat)
+        return self.dims, K, B, step.value
+
+    def load_into(self, renderer):
+        """The current weights into `renderer` (nr_load_mlp builds every pack); returns the renderer."""
+        dims, K, B, _ = self.weights()
+        return renderer.load_mlp(dims, K, B)

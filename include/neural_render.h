@@ -602,6 +602,78 @@ int nr_project_points(nr_ctx *ctx, const float *X /*[n][dims[0]]*/, long n, cons
                       float *distance /*[n]*/, int32_t *iters /*[n]*/, int32_t *status /*[n]*/,
                       int loc, nr_stats *stats);
 
+/* ---- fitting: train a network on the device ------------------------------------------ */
+/* (new symbols and one new struct only: NR_ABI_VERSION stays 3, nr_stats is unchanged)
+ * Fits a [3, 32, ..., 32, 1] ReLU network (nh <= 7 hidden 32 x 32 layers) to (point, value) pairs:
+ * the gradient of the plain or clamped L2 loss with respect to every weight, and Adam, with the
+ * weights, the moments and every sum on the device.  The caller supplies the initial weights in
+ * nr_load_mlp's layout (the device draws no random numbers); nr_fit_weights returns them, and
+ * nr_load_mlp of those builds every pack the renderer uses.  owner supplies the device and the
+ * stream and needs no network; destroy the fit object before its owner.
+ * Flat parameter order (grad, params; P = nr_fit_num_params): K_0, B_0, K_1, B_1, ..., K_last,
+ * B_last, each kernel Keras (in, out) row-major.
+ *
+ * The arithmetic, all f32, one rounding per operation, no contraction except the fmaf named; S =
+ * partials.  n points form ceil(n / 16) tiles of 16 consecutive points; a ragged last tile is
+ * completed with points x = (0, 0, 0) whose e and g (step 2) are +0.0: they take part in every
+ * chain below, where they change no bit unless an accumulator is -0.
+ *  1. Forward: nr_mlp_forward's fp32 pass on the raw weights (each layer an ascending fmaf chain
+ *     from +0, then + bias; a_l = max(z_l, 0), m_l = z_l > 0).  value[p] has the bits nr_mlp_forward
+ *     returns for a context loaded with the same weights.
+ *  2. Residual: with c = clamp > 0, vc = fminf(fmaxf(v, -c), c) and inside = v > -c && v < c; with
+ *     clamp == 0, vc = v and inside = true.  e = vc - y, g = inside ? e : +0.0.
+ *  3. Backward: nr_mlp_gradient's chains seeded with g: d_nh[u] = m_nh[u] ? K_last[u][0] * g : +0.0;
+ *     for l = nh .. 1: acc[i] = chain over j ascending of fmaf(K_l[i][j], d_l[j], acc) from +0,
+ *     d_(l-1)[i] = m_(l-1)[i] ? acc[i] : +0.0.
+ *  4. Partial sums: tile t = p >> 4 belongs to partial t mod S.  Within a partial every sum is one
+ *     chain from +0.0 over the partial's points (completed tiles) in ascending p:
+ *       GK_last[u]: fmaf(a_nh[u], g, .);  GB_last: . + g;  SS: fmaf(e, e, .)
+ *       GK_l[i][j]: fmaf(a_(l-1)[i], d_l[j], .);  GB_l[j]: . + d_l[j]   (l = 1 .. nh)
+ *       GK_0[c][j]: fmaf(x_c, d_0[j], .);  GB_0[j]: . + d_0[j]
+ *  5. Totals, in two levels fixed by S alone: the partials form 16 chunks of C = ceil(S / 16)
+ *     consecutive partials (chunk k: partials k C .. min((k + 1) C, S) - 1; beyond S: empty).
+ *     U_k = +0.0, then U_k = U_k + partial_s over the chunk's s ascending; T = +0.0, then
+ *     T = T + U_k for k = 0 .. 15.  All S partials take part; one with no tile is +0.0.
+ *  6. inv_n = 1.0f / (float)n; loss = SS_T * inv_n; G = T * inv_n.
+ *  7. Adam, step t 1-based and kept in the object.  The host forms in double and rounds to f32:
+ *     a_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), omb1 = 1 - beta1, omb2 = 1 - beta2.  Per
+ *     parameter, m and v from +0:  m = beta1 * m + omb1 * G;  v = beta2 * v + omb2 * (G * G);
+ *     theta = theta - (a_t * m) / (sqrtf(v) + eps), sqrtf and the divide correctly rounded.
+ * No sum depends on grid, the CU count or which wave ran what, and there are no floating-point
+ * atomics: the same arguments give the same bits.
+ *
+ *  - nr_fit_opts: partials = S in 1..4096, 0 = 1024; grid = workgroups of the gradient launch, 0 =
+ *    one per CU (at most ceil(S / 4)), which changes no bit.
+ *  - nr_fit_gradient: loss [1], grad [P], value [n], any of them NULL; loc = NR_HOST or NR_DEVICE
+ *    for all the pointers.  It leaves the weights and the step count alone.
+ *  - nr_fit_run: n / batch Adam steps (n % batch == 0); step k takes rows [k batch, (k + 1) batch)
+ *    as its n points, and loss[k] is their loss before the update.  Two launches per step and no
+ *    synchronisation or read-back between steps; with loc = NR_DEVICE the call only enqueues (the
+ *    step count advances at once).  stats (may be NULL): ray_steps = n, launches, ms_total;
+ *    everything else 0.
+ *  - nr_fit_weights: the master weights params [P] (host) and the steps taken; either may be NULL.
+ * Errors: NR_E_INVALID (a NULL argument, n < 1, n > 2^30, n % batch != 0, lr or eps not finite and
+ * positive, a beta outside [0, 1), clamp negative or not finite, partials outside 0..4096, grid
+ * negative), NR_E_FORMAT (any other shape, 4 inputs included), NR_E_HIP, NR_E_NOMEM.
+ * Memory: 16 P + 4 S (P + 1) bytes and the packs on the device until nr_fit_destroy, and for
+ * NR_HOST callers staging of the points' size. */
+typedef struct nr_fit nr_fit;
+typedef struct nr_fit_opts {
+    float lr, beta1, beta2, eps;  /* Adam */
+    float clamp;                  /* c > 0: the clamped residual; 0: plain */
+    int   partials;               /* S: partial sums, 1..4096; 0 = 1024 */
+    int   grid;                   /* workgroups of the gradient launch; 0 = default */
+} nr_fit_opts;
+int nr_fit_create(nr_ctx *owner, int nlayers, const int *dims, const float *const *kernels,
+                  const float *const *biases, const nr_fit_opts *opts, nr_fit **out);
+int nr_fit_destroy(nr_fit *f);
+int nr_fit_num_params(const nr_fit *f, long *count);
+int nr_fit_gradient(nr_fit *f, const float *X /*[n][3]*/, const float *Y /*[n]*/, long n,
+                    float *loss /*1 or NULL*/, float *grad /*[P] or NULL*/, float *value /*[n] or NULL*/, int loc);
+int nr_fit_run(nr_fit *f, const float *X /*[n][3]*/, const float *Y /*[n]*/, long n, long batch,
+               float *loss /*[n / batch] or NULL*/, int loc, nr_stats *stats);
+int nr_fit_weights(nr_fit *f, float *params /*[P], host*/, long *step);
+
 /* ---- composed scenes: several networks, placed and combined by CSG ---------------- */
 /* (new symbols and new structs only: NR_ABI_VERSION stays 3, nr_stats is unchanged)
  *
