@@ -50,7 +50,12 @@ EXPORTS = [
     "nr_compose_sample_grid", "nr_compose_extract_mesh", "nr_compose_extract_mesh_sparse",
     "nr_compose_render_lit",
     "nr_fit_create", "nr_fit_destroy", "nr_fit_num_params", "nr_fit_gradient", "nr_fit_run", "nr_fit_weights",
+    "nr_obj_load", "nr_trimesh_normals", "nr_trimesh_create", "nr_trimesh_destroy", "nr_trimesh_info",
+    "nr_trimesh_distance",
 ]
+# nr_trimesh_distance: flags, and the feature codes of its `feature` output
+NR_TRIMESH_BRUTE = 1
+NR_TRIMESH_FEATURE = ("face", "edge AB", "edge BC", "edge CA", "vertex A", "vertex B", "vertex C")
 # composed scenes (nr_compose_*): limits and part ops
 NR_COMPOSE_MAX_NETS, NR_COMPOSE_MAX_PARTS = 4, 16
 NR_PART_OP = {"union": 0, "subtract": 1}
@@ -290,6 +295,12 @@ def lib():
         "nr_fit_gradient": (I, [P, P, P, L64, P, P, P, I]),
         "nr_fit_run": (I, [P, P, P, L64, L64, P, I, ctypes.POINTER(NRStats)]),
         "nr_fit_weights": (I, [P, P, ctypes.POINTER(L64)]),
+        "nr_obj_load": (I, [ctypes.c_char_p, ctypes.POINTER(FP), ctypes.POINTER(L64), ctypes.POINTER(IP), ctypes.POINTER(L64)]),
+        "nr_trimesh_normals": (I, [P, L64, P, L64, P, IP]),
+        "nr_trimesh_create": (I, [P, P, L64, P, L64, I, ctypes.POINTER(P)]),
+        "nr_trimesh_destroy": (I, [P]),
+        "nr_trimesh_info": (I, [P, ctypes.POINTER(L64), ctypes.POINTER(L64), ctypes.POINTER(L64), IP, FP, FP, IP]),
+        "nr_trimesh_distance": (I, [P, P, L64, P, P, P, P, I, I, ctypes.POINTER(NRStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -247,6 +247,32 @@ struct SparseArgs {
     int32_t *triangles;           // [nt][3]
 };
 
+// ---- triangle meshes (nr_trimesh_host.cpp: host only; nr_trimesh.hip k_trimesh_distance) ----
+// The OBJ reader behind nr_obj_load: `v` and `f` records, triangles as fans; NR_OK, NR_E_IO or NR_E_FORMAT.
+int obj_parse(const char *path, std::vector<float> &V, std::vector<int32_t> &T, std::string &err);
+bool trimesh_indices_ok(const int32_t *T, long nt, long nv);
+// nr_trimesh_normals on checked arguments (table [nt][7][3] or NULL, closed or NULL)
+void trimesh_normals(const float *V, long nv, const int32_t *T, long nt, float *table, int *closed);
+// The hierarchy over the triangles whose face entry in `table` is not zero, in device layout:
+//   nodes  8 words each: lo.xyz, first | left, hi.xyz, -count | right -- the inflated box, then a leaf's
+//          triangles [first, first + count) of `tris` (word 7 <= 0) or an inner node's children (word 7
+//          > 0; the root is node 0, so no child is).  Preorder: a node, its left subtree, its right one.
+//   tris   12 words each, leaf by leaf: a.xyz, original index, b.xyz, 0, c.xyz, 0
+// Boxes are inflated by slack = 2^-TRIMESH_SLACK_SHIFT (largest |coordinate| + largest axis extent)
+// and rounded outward.  False when the depth exceeds ceil(log2 ntl) + 1 or TRIMESH_STACK (the wave's
+// stack in k_trimesh_distance holds one pending child per level).
+constexpr int TRIMESH_SLACK_SHIFT = 18;
+constexpr int TRIMESH_STACK = 32;
+constexpr int TRIMESH_LEAF_DEFAULT = 8;
+struct TriBvh {
+    std::vector<float> nodes, tris;
+    long nnodes = 0, ntl = 0;
+    int depth = 0;
+    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // the vertices' bound, not inflated
+    float slack = 0;
+};
+bool trimesh_build(const float *V, long nv, const int32_t *T, long nt, int leaf, const float *table, TriBvh &out);
+
 // ---- context internals for nr_group.hip (nr_api.hip) ----
 int ctx_device(const nr_ctx *c);
 void *ctx_stream(nr_ctx *c);  // the hipStream_t the context's work runs on (creates its own stream if selected)

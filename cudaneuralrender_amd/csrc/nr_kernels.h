@@ -304,6 +304,21 @@ struct ProjArgs {
     unsigned long long *stats;    // [0] evaluations, [1] converged points, [2] the largest evaluation count
 };
 
+// Signed distance to a triangle mesh (nr_trimesh.hip k_trimesh_distance; nr_trimesh_distance): every
+// point writes its slot of the outputs that are not NULL.  nodes / tris: nr_internal.h TriBvh.
+struct TriMeshArgs {
+    const float *X;               // [n][3]
+    long n;                       // 1 .. 2^30
+    const float *nodes, *tris;    // [nnodes][8], [ntl][12]
+    const float *table;           // [nt][7][3] pseudonormals, original triangle order
+    int nnodes, ntl;
+    int brute;                    // every triangle of tris in order, no hierarchy
+    float *sdf, *closest;         // [n], [n][3]
+    int32_t *tri, *feature;       // [n]
+    unsigned long long *stats;    // [0] point-triangle evaluations (zeroed before the launch)
+};
+hipError_t launch_trimesh_distance(const TriMeshArgs &A, int grid, hipStream_t st);  // 4-wave workgroups
+
 // Composed scenes (nr_compose.hip; nr_compose_*): the distinct fp32 packs back to back in one device
 // buffer (staged into dynamic LDS in that order), the parts, and the queried rays or points.  The
 // struct travels in the kernarg segment: the part loop is wave-uniform and reads it with scalar loads.

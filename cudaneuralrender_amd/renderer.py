@@ -13,6 +13,7 @@ from ._lib import (NR_AA_CONTRAST_DEFAULT, NR_AA_MODE, NR_COLOR_FACING, NR_COLOR
                    NR_GROUP_COPY, NR_HOST, NR_PRECISION, NR_SCENE, NR_SCHEDULE, NRFrame, NRKernelProf, NRLight, NRProjectOpts,
                    NRStats, check, lib)
 from ._lib import NR_PART_OP, NRComposeStats, NRFitOpts, NRPart
+from ._lib import NR_TRIMESH_BRUTE
 
 _FP = ctypes.POINTER(ctypes.c_float)
 
@@ -97,6 +98,42 @@ def save_obj(path, vertices, triangles, normals=None):
         raise ValueError(f"normals {N.shape} and vertices {V.shape} differ")
     check(lib().nr_obj_save(str(path).encode(), V.ctypes.data, V.shape[0], None if N is None else N.ctypes.data,
                             T.ctypes.data, T.shape[0]))
+
+
+def load_obj(path):
+    """nr_obj_load: (V [nv, 3] float32, F [nt, 3] int32) of a Wavefront OBJ -- `v` and `f` records, 1-based or
+    negative indices, i/t/n corners, polygons as fans from their first corner."""
+    L = lib()
+    vp, tp = _FP(), ctypes.POINTER(ctypes.c_int)()
+    nv, nt = ctypes.c_long(0), ctypes.c_long(0)
+    check(L.nr_obj_load(str(path).encode(), ctypes.byref(vp), ctypes.byref(nv), ctypes.byref(tp), ctypes.byref(nt)))
+    try:
+        V = np.ctypeslib.as_array(vp, shape=(nv.value * 3,)).copy() if nv.value else np.zeros(0, np.float32)
+        T = np.ctypeslib.as_array(tp, shape=(nt.value * 3,)).copy() if nt.value else np.zeros(0, np.int32)
+    finally:
+        L.nr_free(ctypes.cast(vp, ctypes.c_void_p))
+        L.nr_free(ctypes.cast(tp, ctypes.c_void_p))
+    return V.reshape(-1, 3).astype(np.float32, copy=False), T.reshape(-1, 3).astype(np.int32, copy=False)
+
+
+def _mesh_arrays(vertices, triangles):
+    V = np.ascontiguousarray(vertices, np.float32)
+    T = np.ascontiguousarray(triangles, np.int32)
+    if V.ndim != 2 or V.shape[1] != 3 or T.ndim != 2 or T.shape[1] != 3:
+        raise ValueError(f"vertices must be [nv, 3] and triangles [nt, 3], got {V.shape} and {T.shape}")
+    return V, T
+
+
+def trimesh_normals(vertices, triangles):
+    """nr_trimesh_normals: (table [nt, 7, 3] float32, closed) -- the angle-weighted pseudonormals of every
+    triangle's face, edges AB, BC, CA and vertices A, B, C (not normalised), and whether the mesh is
+    closed and consistently wound."""
+    V, T = _mesh_arrays(vertices, triangles)
+    table = np.zeros((T.shape[0], 7, 3), np.float32)
+    closed = ctypes.c_int(0)
+    check(lib().nr_trimesh_normals(V.ctypes.data, V.shape[0], T.ctypes.data, T.shape[0], table.ctypes.data,
+                                   ctypes.byref(closed)))
+    return table, bool(closed.value)
 
 
 def _lattice(origin, step, dims):
@@ -1294,3 +1331,82 @@ class Fit:
         """The current weights into `renderer` (nr_load_mlp builds every pack); returns the renderer."""
         dims, K, B, _ = self.weights()
         return renderer.load_mlp(dims, K, B)
+
+
+class TriMesh:
+    """nr_trimesh: a triangle mesh, its pseudonormals and a box hierarchy on the device, queried for the
+    signed distance of points -- bit for bit the arithmetic written in include/neural_render.h.
+    `renderer` supplies the device and the stream (it needs no network).  leaf: triangles per leaf of
+    the hierarchy, 0 = 8.  Close the mesh before its renderer."""
+
+    def __init__(self, renderer, vertices, triangles, leaf=0):
+        self._L = lib()
+        self.owner = renderer
+        self._m = ctypes.c_void_p()
+        V, T = _mesh_arrays(vertices, triangles)
+        renderer._chk(self._L.nr_trimesh_create(renderer._ctx, V.ctypes.data, V.shape[0], T.ctypes.data, T.shape[0],
+                                                int(leaf), ctypes.byref(self._m)))
+
+    def close(self):
+        if self._m:
+            # (the C object reaches through its owner: after an owner closed first it is left alone)
+            if self.owner._ctx:
+                self._L.nr_trimesh_destroy(self._m)
+            self._m = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _chk(self, rc):
+        return check(rc, self.owner._ctx)
+
+    def info(self):
+        """{"nv", "nt", "nodes", "depth", "lo", "hi", "closed"}: the mesh, its hierarchy and its bound."""
+        nv, nt, nodes = ctypes.c_long(0), ctypes.c_long(0), ctypes.c_long(0)
+        depth, closed = ctypes.c_int(0), ctypes.c_int(0)
+        lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        self._chk(self._L.nr_trimesh_info(self._m, ctypes.byref(nv), ctypes.byref(nt), ctypes.byref(nodes),
+                                          ctypes.byref(depth), _fptr(lo), _fptr(hi), ctypes.byref(closed)))
+        return {"nv": nv.value, "nt": nt.value, "nodes": nodes.value, "depth": depth.value, "lo": lo, "hi": hi,
+                "closed": bool(closed.value)}
+
+    def distance(self, X, closest=False, tri=False, feature=False, brute=False, with_stats=False):
+        """nr_trimesh_distance on a host array X [n, 3]: {"sdf" [n][, "closest" [n, 3], "tri" [n] int32,
+        "feature" [n] int32]} -- negative inside a closed mesh whose triangles wind outward.  brute:
+        every triangle, no hierarchy (the same bits).  Neighbours in space should be neighbours in X."""
+        X = np.ascontiguousarray(X, np.float32)
+        if X.ndim != 2 or X.shape[1] != 3:
+            raise ValueError(f"X must be [n, 3], got {X.shape}")
+        n = X.shape[0]
+        out = {"sdf": np.zeros(n, np.float32)}
+        if closest:
+            out["closest"] = np.zeros((n, 3), np.float32)
+        if tri:
+            out["tri"] = np.zeros(n, np.int32)
+        if feature:
+            out["feature"] = np.zeros(n, np.int32)
+        ptr = [out[k].ctypes.data if k in out else None for k in ("sdf", "closest", "tri", "feature")]
+        st = NRStats()
+        self._chk(self._L.nr_trimesh_distance(self._m, X.ctypes.data, n, *ptr, NR_TRIMESH_BRUTE if brute else 0, NR_HOST,
+                                              ctypes.byref(st) if with_stats else None))
+        return (out, st.as_dict()) if with_stats else out
+
+    def distance_device(self, x_ptr, n, sdf_ptr=None, closest_ptr=None, tri_ptr=None, feature_ptr=None, brute=False,
+                        with_stats=False):
+        """nr_trimesh_distance on device buffers (float32 X [n, 3], sdf [n], closest [n, 3], int32 tri [n],
+        feature [n]); None = that output is not wanted.  Runs on the renderer's stream and, without
+        stats, returns without waiting."""
+        vp = [ctypes.c_void_p(p) if p else None for p in (x_ptr, sdf_ptr, closest_ptr, tri_ptr, feature_ptr)]
+        st = NRStats()
+        self._chk(self._L.nr_trimesh_distance(self._m, vp[0], int(n), *vp[1:], NR_TRIMESH_BRUTE if brute else 0, NR_DEVICE,
+                                              ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None

@@ -674,6 +674,104 @@ int nr_fit_run(nr_fit *f, const float *X /*[n][3]*/, const float *Y /*[n]*/, lon
                float *loss /*[n / batch] or NULL*/, int loc, nr_stats *stats);
 int nr_fit_weights(nr_fit *f, float *params /*[P], host*/, long *step);
 
+/* ---- triangle meshes: signed distance from points to a mesh ------------------------- */
+/* (new symbols only: NR_ABI_VERSION stays 3, nr_stats is unchanged)
+ * nr_obj_load reads a Wavefront OBJ; nr_trimesh_normals builds the pseudonormal table of a mesh;
+ * a nr_trimesh holds a mesh, its table and a bounding-box hierarchy on the device, and
+ * nr_trimesh_distance gives, per point, the signed distance to the mesh, the closest point, its
+ * triangle and the feature of the triangle it lies on.  owner supplies the device and the stream and
+ * needs no network; destroy the mesh object before its owner.
+ *
+ * nr_obj_load (host only).  Records `v x y z [w]` (w ignored) and `f` with corners i, i/t, i//n or
+ * i/t/n, 1-based or negative (relative to the vertices read so far); a face of more than three
+ * corners becomes a fan from its first corner.  Every other record is ignored.  NR_E_IO: the file
+ * cannot be read.  NR_E_FORMAT: a vertex without three numbers, a corner that is no index, an index
+ * out of range, a face of fewer than 3 corners.  vertices [nv][3] and triangles [nt][3] (0-based) are
+ * the caller's to nr_free.  nr_obj_save -> nr_obj_load returns the same bits (%.9g round-trips f32).
+ *
+ * The pseudonormal table N [nt][7][3] (nr_trimesh_normals, host only): entry 0 the face, 1..3 the
+ * edges AB, BC, CA, 4..6 the vertices A, B, C of triangle (A, B, C).  Computed in double from the f32
+ * coordinates and rounded to f32 once, not normalised (only the direction is used):
+ *   face    (b - a) x (c - a), normalised; a triangle whose cross product is 0 (zero area) or not
+ *           finite has face entry (0, 0, 0);
+ *   edge    the sum of the (double) face normals of every triangle that uses the undirected edge, in
+ *           ascending triangle index; every triangle of the edge gets the same bits;
+ *   vertex  the sum over the triangles that use the vertex, ascending triangle index, of angle * face
+ *           normal, angle = atan2(|u x v|, u . v) of the two edges u, v leaving that corner;
+ *           zero-area triangles are left out.
+ * Vertices are identified by index, never by position.  closed = 1 iff every undirected edge is used
+ * by exactly two triangles, once in each direction, and joins two different vertices.
+ *
+ * The distance, all f32, one rounding per operation, no contraction except the fmaf named.  For
+ * vectors dot(u, v) = fmaf(u.z, v.z, fmaf(u.y, v.y, u.x * v.x)); differences and fmaf of vectors are
+ * componentwise.
+ *  1. Per triangle (a, b, c) and point p (Ericson, Real-Time Collision Detection 5.1.5):
+ *       ab = b - a, ac = c - a, bc = c - b, ap = p - a, bp = p - b, cp = p - c
+ *       d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp),
+ *       d6 = dot(ac, cp);  vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4
+ *       (two products and one subtraction each);  e43 = d4 - d3, e56 = d5 - d6.
+ *     The first region that holds, in this order, gives the closest point q and the feature:
+ *       4 (A)   d1 <= 0 && d2 <= 0:                q = a
+ *       5 (B)   d3 >= 0 && d4 <= d3:               q = b
+ *       1 (AB)  vc <= 0 && d1 >= 0 && d3 <= 0:     q = fmaf(ab, d1 / (d1 - d3), a)
+ *       6 (C)   d6 >= 0 && d5 <= d6:               q = c
+ *       3 (CA)  vb <= 0 && d2 >= 0 && d6 <= 0:     q = fmaf(ac, d2 / (d2 - d6), a)
+ *       2 (BC)  va <= 0 && e43 >= 0 && e56 >= 0:   q = fmaf(bc, e43 / (e43 + e56), b)
+ *       0 (face) otherwise: den = (va + vb) + vc;  q = fmaf(ac, vc / den, fmaf(ab, vb / den, a))
+ *     (every quotient one correctly rounded division; a comparison with a NaN is false).
+ *     d2(t) = dot(p - q, p - q).  A zero-area triangle (face entry (0, 0, 0)) has d2 = NaN by
+ *     definition, whatever its corners.
+ *  2. The winner is the triangle with the lexicographic minimum of (d2, triangle index) over all
+ *     triangles of the mesh; a NaN d2 never wins (every comparison is d2 < best, or d2 == best with
+ *     the smaller index).  A minimum does not depend on the order it is taken in: the result is the
+ *     same bits for any traversal, leaf size, grid, or with NR_TRIMESH_BRUTE.  closest = q and
+ *     feature of the winner (step 1 once more), tri = its index in the caller's triangles,
+ *     d = sqrtf(d2), correctly rounded.
+ *  3. Sign: s = dot(p - q, N[tri][feature]); sdf = s < 0 ? -d : d.  With the library's meshes
+ *     ((b - a) x (c - a) points outward: step 4 of nr_mesh_grid) inside is negative.  The sign means
+ *     something only for a closed mesh (closed = 1); otherwise it is computed all the same.
+ *  4. A point with a non-finite coordinate, or a mesh of zero-area triangles only, gives sdf = closest =
+ *     the quiet NaN 0x7fc00000 and tri = feature = -1.
+ * The hierarchy (built by nr_trimesh_create on the host): a binary tree over the triangles' boxes,
+ * split at the median of the centroids along the axis of their largest extent, ordered by
+ * (coordinate, triangle index), until a node holds at most `leaf` triangles (0 = 8); its depth is at
+ * most ceil(log2 nt) + 1 (checked against the walk's stack of 32 levels).  Every box is grown by
+ * slack = 2^-18 (largest |coordinate| + largest axis extent of the vertices) and rounded outward; a
+ * point's bound to a box is lb = 0.9999847412109375f (1 - 2^-16) * dot(g, g) with g the componentwise
+ * gap max(lo - p, p - hi, 0), and a node is left out only when lb > best for every point that shares
+ * the walk.  The result is therefore that of step 2 whenever every computed q lies inside its
+ * triangle's grown box -- always, except for slivers whose quotients are rounding noise; with
+ * NR_TRIMESH_BRUTE unconditionally.
+ *
+ *  - nr_trimesh_distance: any of sdf [n], closest [n][3], tri [n], feature [n] may be NULL; loc =
+ *    NR_HOST or NR_DEVICE for X and all of them.  One launch; with loc = NR_DEVICE and no stats the
+ *    call only enqueues.  Points are taken 64 at a time in the order given and the 64 share one walk:
+ *    points that are neighbours in space should be neighbours in X (the call does not sort).
+ *    stats (may be NULL): ray_steps = n, shade_evals = point-triangle evaluations done (summed over
+ *    the points), launches, ms_total; everything else 0.
+ *  - nr_trimesh_info: any output may be NULL; lo, hi = the vertices' bound (not grown); nodes and
+ *    depth of the hierarchy.
+ * Errors: NR_E_INVALID (a NULL owner, mesh, vertices, triangles, out or X; nv < 1; nt < 1; nt > 2^24;
+ * an index outside 0..nv - 1; a vertex that is not finite; leaf outside 0..32; n < 1; n > 2^30; a flag
+ * bit other than NR_TRIMESH_BRUTE), NR_E_IO and NR_E_FORMAT (nr_obj_load), NR_E_HIP, NR_E_NOMEM.
+ * Memory on the device until nr_trimesh_destroy: 132 bytes per triangle (48: the reordered corners
+ * and index; 84: the table) and 32 bytes per node (at most 2 ceil(nt / ceil(leaf / 2)) nodes), and for
+ * NR_HOST callers staging of the points' and outputs' size. */
+typedef struct nr_trimesh nr_trimesh;
+#define NR_TRIMESH_BRUTE 1   /* visit every triangle, no hierarchy: the cross-check and the baseline */
+int nr_obj_load(const char *path, float **vertices /*[nv][3]*/, long *nv, int32_t **triangles /*[nt][3]*/, long *nt);
+int nr_trimesh_normals(const float *vertices /*[nv][3]*/, long nv, const int32_t *triangles /*[nt][3]*/, long nt,
+                       float *table /*[nt][7][3] or NULL*/, int *closed /*or NULL*/);
+int nr_trimesh_create(nr_ctx *owner, const float *vertices /*[nv][3], host*/, long nv,
+                      const int32_t *triangles /*[nt][3], host*/, long nt, int leaf /*0 = 8, else 1..32*/,
+                      nr_trimesh **out);
+int nr_trimesh_destroy(nr_trimesh *m);
+int nr_trimesh_info(const nr_trimesh *m, long *nv, long *nt, long *nodes, int *depth, float lo[3], float hi[3],
+                    int *closed);
+int nr_trimesh_distance(nr_trimesh *m, const float *X /*[n][3]*/, long n, float *sdf /*[n]*/,
+                        float *closest /*[n][3]*/, int32_t *tri /*[n]*/, int32_t *feature /*[n]*/, int flags,
+                        int loc, nr_stats *stats);
+
 /* ---- composed scenes: several networks, placed and combined by CSG ---------------- */
 /* (new symbols and new structs only: NR_ABI_VERSION stays 3, nr_stats is unchanged)
  *

@@ -1,0 +1,120 @@
+"""OBJ -> samples -> Fit -> load_into -> render, once, printing what it did.
+
+The mesh: an OBJ file (nr.load_obj), or with no argument the mesh nr_extract_mesh gives for plane_1
+(scene tanh, --size^3 lattice over [-1, 1]^3).  The samples, fit_bench's recipe with the mesh in the
+network's place: --points / 2 points uniform in the ball of radius 1.2 about the mesh (its bound scaled
+into the unit ball), as many on the surface -- the closest points nr_trimesh_distance returns for ball
+points -- jittered by 0.03; the query runs on a Morton-sorted copy (neighbours in space share a walk) and
+the pairs are shuffled afterwards for the fit.  Y = the signed distance, clamp 0.1; a [3, 32 x 4, 1]
+student, batch 2^16, lr 1e-3, --epochs epochs; then load_into a renderer and a 256^2 frame, whose
+silhouette is compared with the source network's when the mesh came from one.
+Runs on the GPU box: python3 tools/fit_mesh.py [mesh.obj]"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch  # device buffers; initialised before libnr
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import cudaneuralrender_amd as nr  # noqa: E402
+from fit_bench import CLAMP, init_net, silhouette  # noqa: E402
+from trimesh_bench import morton_order  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("obj", nargs="?")
+    ap.add_argument("--size", type=int, default=128)
+    ap.add_argument("--points", type=int, default=1 << 21)
+    ap.add_argument("--epochs", type=int, default=400)
+    ap.add_argument("--out", help="write the student's frame here (.png)")
+    args = ap.parse_args()
+    n = args.points
+    dev = torch.device("cuda:0")
+    torch.cuda.init()
+    stream = torch.cuda.current_stream(dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(5)
+
+    source = None
+    if args.obj:
+        V, T = nr.load_obj(args.obj)
+        print(f"{args.obj}: {len(V)} vertices, {len(T)} triangles")
+        # into the unit ball, as the bundled networks' shapes are
+        mid = (V.min(0) + V.max(0)) / 2
+        V = ((V - mid) / np.float32(np.linalg.norm(V - mid, axis=1).max() * 1.05)).astype(np.float32)
+    else:
+        source = nr.Renderer(0)
+        source.load_h5(nr.geometry_path("plane_1")).set_precision("fp32").set_scene("tanh")
+        step = np.float32(2.0) / np.float32(args.size - 1)
+        mesh = source.extract_mesh((-1.0, -1.0, -1.0), (step, step, step), (args.size,) * 3, normals=False)
+        V, T = mesh["vertices"], mesh["triangles"]
+        print(f"plane_1 through nr_extract_mesh at {args.size}^3: {len(V)} vertices, {len(T)} triangles")
+    owner = nr.Renderer(0)
+    owner.set_stream(stream.cuda_stream)
+    with nr.TriMesh(owner, V, T) as m:
+        info = m.info()
+        print(f"TriMesh: {info['nodes']} nodes, depth {info['depth']}, closed {info['closed']}")
+        if not info["closed"]:
+            print("the mesh is not closed: the sign of the distance means nothing, and so does the fit")
+        d = torch.randn((n // 2, 3), generator=gen, device=dev)
+        u = torch.rand((n // 2, 1), generator=gen, device=dev)
+        ball = (d / d.norm(dim=1, keepdim=True) * 1.2 * u.pow(1.0 / 3.0)).float()
+        ball = ball[morton_order(ball, -1.3, 1.3)].contiguous()
+        surf = torch.zeros_like(ball)
+        torch.cuda.synchronize()
+        st0 = m.distance_device(ball.data_ptr(), n // 2, closest_ptr=surf.data_ptr(), with_stats=True)
+        surf = surf + 0.03 * torch.randn(surf.shape, generator=gen, device=dev)
+        X = torch.cat([ball, surf])
+        X = X[morton_order(X, -1.3, 1.3)].float().contiguous()
+        Y = torch.zeros(n, dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        st1 = m.distance_device(X.data_ptr(), n, Y.data_ptr(), with_stats=True)
+    print(f"samples: {n // 2} ball points -> closest points in {st0['ms_total']:.2f} ms ({st0['shade_evals'] / (n // 2):.1f} "
+          f"evaluations per point); {n} signed distances in {st1['ms_total']:.2f} ms ({st1['shade_evals'] / n:.1f} per point); "
+          f"{float((Y < 0).float().mean()):.4f} of them inside, |Y| < clamp at {float((Y.abs() < CLAMP).float().mean()):.3f}")
+    perm = torch.randperm(n, generator=gen, device=dev)
+    X, Y = X[perm].contiguous(), Y[perm].contiguous()
+
+    dims, K, B = init_net(3, 20)
+    batch = 1 << 16
+    steps = n // batch
+    losses = torch.zeros(steps, dtype=torch.float32, device=dev)
+    curve = []
+    torch.cuda.synchronize()
+    with nr.Fit(owner, dims, K, B, lr=1e-3, clamp=CLAMP) as f:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for ep in range(args.epochs):
+            f.run_device(X.data_ptr(), Y.data_ptr(), steps * batch, batch, losses.data_ptr())
+            curve.append(losses.mean())
+        e1.record(stream)
+        e1.synchronize()
+        student = nr.Renderer(0)
+        f.load_into(student)
+        step_count = f.weights()[3]
+    curve = [float(c) for c in curve]
+    floor = float(((Y.clamp(-CLAMP, CLAMP) - Y) ** 2).mean())
+    print(f"fit: [3, 32 x 4, 1], batch 2^16, lr 1e-3, clamp {CLAMP}, {args.epochs} epochs = {step_count} steps in "
+          f"{e0.elapsed_time(e1):.1f} ms (host loop included); loss of every tenth epoch: "
+          + " ".join(f"{c:.3e}" for c in curve[::10]) + f"; last {curve[-1]:.3e}")
+    print(f"loss of a student equal to the distance (Y is not clamped): {floor:.3e}")
+    ss = silhouette(student)
+    if args.out:
+        img, _ = student.render(256, 256, 256)
+        nr.save_png(args.out, img)
+    if source is not None:
+        st = silhouette(source)
+        print(f"silhouette at 256^2: source network {int(st.sum())} px, student fitted to its mesh {int(ss.sum())} px, "
+              f"IoU {float((st & ss).sum() / max((st | ss).sum(), 1)):.4f}")
+        source.close()
+    else:
+        print(f"silhouette at 256^2: student {int(ss.sum())} px (no source network to compare with)")
+    student.close()
+    owner.close()
+
+
+if __name__ == "__main__":
+    main()
