@@ -525,28 +525,76 @@ __device__ __forceinline__ float mlp16_fp32_pruned(const MlpArgs &M, const float
 // Cost (profiles/unit_skip_peak.txt): 64 cycles per issued unit, the 16x16x4 rate; about 8.5
 // cycles per tested unit when a group's tests precede its branches (15 with test and branch
 // alternating), about 10 per v_permlane32_swap.
-// units per group of tests, 4 or 8: a group's tests come before its branches.  8 measured 4 % faster
-// than 4 on the headline (profiles/unit_skip_bench.txt), within the same registers
-#ifndef NR_UNIT_GROUP
-#define NR_UNIT_GROUP 8
-#endif
+//
+// LDS reads (profiles/unit_pipeline.txt).  The weights of four units are one ds_read_b128 per lane
+// (lanes l and l + 32 the same 16 bytes, consecutive rows 16 bytes apart: no bank conflict), issued
+// from inline asm four units ahead of their use, so that it is in flight while the four before run
+// their instructions (eight ahead would hold 8 more VGPRs, which the tracer does not have); the
+// first four of a layer are read during the epilogue of the layer before, and of the epilogue's
+// four bias reads two are issued before the last four units' branches and two at its start.  The
+// compiler does not know that these registers are pending: every use is behind units_wait, which
+// waits for all LDS reads of the wave (lgkmcnt(0): reads return in order, and the reads of one
+// step are all that is in flight) and passes the registers through, so that no use can move above
+// it; every wait comes before the loop's back edge, so that no pending register crosses it.
+// Written as plain loads, hipcc split the reads into ds_read_b32 / ds_read2_b32 (4-byte reads at a
+// 16-byte lane stride: bank conflicts on half of the LDS cycles) and sank one of them to
+// directly in front of the first instruction of each group.
+//
+// Units per group of tests: a group's tests come before its branches.  8 measured 4 % faster than 4
+// on the headline (profiles/unit_skip_bench.txt); 16 and 32, all of a layer's tests before its first
+// branch, measured the same as 8 (profiles/unit_pipeline.txt).
+constexpr int UNIT_GROUP = 8;
 typedef float f32x32 __attribute__((ext_vector_type(32)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ constexpr int unit_reg(int u) { return 16 * ((u >> 2) & 1) + (u & 3) + 4 * (u >> 3); }
 
-// the epilogue of a layer: c (D layout) -> a (every lane its own point's activations)
+// LDS byte address of a pointer into the staged pack
+__device__ __forceinline__ uint32_t lds_addr(const float *p) {
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float *)p;
+}
+// the weights of units 4k .. 4k + 3 of the lane's row, OFF = 512 k; addr: the layer's weights + 16 row
+template <int OFF>
+__device__ __forceinline__ void units_wread(uint32_t addr, f32x4 &w) {
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(w) : "v"(addr), "n"(OFF));
+}
+// the bias of the lane's rows 8q + 4h .. + 3 for q = Q and Q + 1; addr: the layer's bias + 16 h
+template <int Q>
+__device__ __forceinline__ void units_bread(uint32_t addr, f32x4 &b0, f32x4 &b1) {
+    asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4"
+                 : "=&v"(b0), "=&v"(b1)
+                 : "v"(addr), "n"(32 * Q), "n"(32 * Q + 32));
+}
+__device__ __forceinline__ void units_wait(f32x4 &w) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(w)); }
+__device__ __forceinline__ void units_wait(f32x4 &b0, f32x4 &b1) {
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(b0), "+v"(b1));
+}
+__device__ __forceinline__ void units_wait(f32x4 &w, f32x4 &b0, f32x4 &b1) {
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(w), "+v"(b0), "+v"(b1));
+}
+
+// The epilogue of a layer: c (D layout) -> a (every lane its own point's activations).  b0, b1: the
+// bias of the lane's rows for q = 0, 1, read (units_bread<0>) but not yet waited for; ba: the
+// layer's bias + 16 h.  The other half of the bias and the first four weights of the layer to come
+// (wa; into w, settled on return) are read here, into registers that the layer's inputs have left,
+// and are in flight during the first half's adds.
 template <bool L0>
-__device__ __forceinline__ void units_epilogue(const f32x32 &c, f32x32 &a, const float *bias, float s0, int h) {
-    const float4 *bb = reinterpret_cast<const float4 *>(bias + 4 * h);
+__device__ __forceinline__ void units_epilogue(const f32x32 &c, f32x32 &a, f32x4 &b0, f32x4 &b1, uint32_t ba, float s0,
+                                               uint32_t wa, f32x4 &w) {
+    f32x4 b2, b3;
+    units_wait(b0, b1);
+    units_bread<2>(ba, b2, b3);
+    units_wread<0>(wa, w);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const float4 b4 = bb[2 * q];  // rows 8q + 4h .. + 3
-        const float b[4] = {b4.x, b4.y, b4.z, b4.w};
+        if (q == 2) units_wait(w, b2, b3);
+        const f32x4 &bq = q == 0 ? b0 : q == 1 ? b1 : q == 2 ? b2 : b3;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int r = 4 * q + i;
+            const float b = bq[i];
             // (layer 0: its weights are unscaled; fma(c, 2^-e0, b 2^-e0) = (c + b) 2^-e0 in one rounding)
-            a[r] = __builtin_amdgcn_fmed3f(L0 ? __builtin_fmaf(c[r], s0, b[i]) : c[r] + b[i], 0.0f, 1.0f);
-            a[16 + r] = __builtin_amdgcn_fmed3f(L0 ? __builtin_fmaf(c[16 + r], s0, b[i]) : c[16 + r] + b[i], 0.0f, 1.0f);
+            a[r] = __builtin_amdgcn_fmed3f(L0 ? __builtin_fmaf(c[r], s0, b) : c[r] + b, 0.0f, 1.0f);
+            a[16 + r] = __builtin_amdgcn_fmed3f(L0 ? __builtin_fmaf(c[16 + r], s0, b) : c[16 + r] + b, 0.0f, 1.0f);
         }
     }
 #pragma unroll
@@ -566,43 +614,63 @@ __device__ __forceinline__ float mlp64_fp32_units(const float *__restrict__ s, i
     asm volatile("" : "+v"(lane));
     const int row = lane & 31, h = lane >> 5;
     f32x32 a, c;
+    // wa: the first hidden layer's weights + 16 row (without a hidden layer, layer 0's, which nothing
+    // uses: every prefetch stays inside the pack); ba: layer 0's bias + 16 h
+    uint32_t wa = lds_addr(s) + 4u * (nh > 0 ? PK_HID : 0) + 16u * row;
+    uint32_t ba = lds_addr(s) + 4u * PK_L0B + 16u * h;
+    f32x4 w;  // the weights of the four units at hand
     {
-        const float *w = s + PK_L0W + row;
-        c = __builtin_amdgcn_mfma_f32_32x32x1f32(w[0], x, f32x32{}, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x1f32(w[32], y, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x1f32(w[64], z, c, 0, 0, 0);
-        if (in0 == 4) c = __builtin_amdgcn_mfma_f32_32x32x1f32(w[96], fr, c, 0, 0, 0);
-        units_epilogue<true>(c, a, s + PK_L0B, s[pk_final(nh) + 33], h);
+        f32x4 b0, b1;
+        units_bread<0>(ba, b0, b1);
+        const float *w0 = s + PK_L0W + row;
+        c = __builtin_amdgcn_mfma_f32_32x32x1f32(w0[0], x, f32x32{}, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x1f32(w0[32], y, c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x1f32(w0[64], z, c, 0, 0, 0);
+        if (in0 == 4) c = __builtin_amdgcn_mfma_f32_32x32x1f32(w0[96], fr, c, 0, 0, 0);
+        units_epilogue<true>(c, a, b0, b1, ba, s[pk_final(nh) + 33], wa, w);
     }
+    ba += 4u * (PK_HID + 1024 - PK_L0B);
     uint32_t ni = 0;  // instructions issued behind a branch
-    constexpr int UG = NR_UNIT_GROUP;  // units per group of tests: 4 or 8
+    constexpr int UG = UNIT_GROUP;
     for (int jl = 0; jl < nh; ++jl) {
-        const float *L = s + PK_HID + jl * PK_HID_STRIDE;
-        const float4 *W4 = reinterpret_cast<const float4 *>(L) + row;
+        f32x4 b0, b1;
+        unsigned long long m[UG];
 #pragma unroll
-        for (int g = 0; g < 32 / UG; ++g) {  // units UG g .. UG g + UG - 1: their tests first, then a branch each
-            float w[UG];
+        for (int k = 0; k < 8; ++k) {  // units 4 k .. 4 k + 3
+            if (4 * k % UG == 0) {
 #pragma unroll
-            for (int q = 0; q < UG / 4; ++q) {
-                const float4 wv = W4[(UG / 4 * g + q) * 32];
-                w[4 * q] = wv.x; w[4 * q + 1] = wv.y; w[4 * q + 2] = wv.z; w[4 * q + 3] = wv.w;
+                for (int i = 0; i < UG; ++i)
+                    m[i] = __builtin_amdgcn_ballot_w64(__float_as_uint(a[unit_reg(4 * k + i)]) != 0u) & live;
             }
-            unsigned long long m[UG];
+            // the next four weights, into other registers than these; after the last four the
+            // first half of the bias
+            f32x4 n;
+            if (k == 0) units_wread<512>(wa, n);
+            if (k == 1) units_wread<1024>(wa, n);
+            if (k == 2) units_wread<1536>(wa, n);
+            if (k == 3) units_wread<2048>(wa, n);
+            if (k == 4) units_wread<2560>(wa, n);
+            if (k == 5) units_wread<3072>(wa, n);
+            if (k == 6) units_wread<3584>(wa, n);
+            if (k == 7) units_bread<0>(ba, b0, b1);
 #pragma unroll
-            for (int i = 0; i < UG; ++i) {
-                m[i] = __builtin_amdgcn_ballot_w64(__float_as_uint(a[unit_reg(UG * g + i)]) != 0u) & live;
-            }
-#pragma unroll
-            for (int i = 0; i < UG; ++i) {
-                const int u = UG * g + i;
+            for (int i = 0; i < 4; ++i) {
+                const int u = 4 * k + i;
                 if (u == 0) c = __builtin_amdgcn_mfma_f32_32x32x1f32(w[i], a[unit_reg(u)], f32x32{}, 0, 0, 0);
-                else if (m[i]) {
+                else if (m[u % UG]) {
                     c = __builtin_amdgcn_mfma_f32_32x32x1f32(w[i], a[unit_reg(u)], c, 0, 0, 0);
                     ++ni;  // (a scalar add beside the instruction: no else)
                 }
             }
+            if (k < 7) {
+                units_wait(n);
+                w = n;
+            }
         }
-        units_epilogue<false>(c, a, L + 1024, 0.0f, h);
+        // (after the last layer, its own first weights again: inside the pack)
+        if (jl + 1 < nh) wa += 4u * PK_HID_STRIDE;
+        units_epilogue<false>(c, a, b0, b1, ba, 0.0f, wa, w);
+        ba += 4u * PK_HID_STRIDE;
     }
     nskip += 31u * (uint32_t)nh - ni;
     const float4 *wf4 = reinterpret_cast<const float4 *>(s + pk_final(nh));

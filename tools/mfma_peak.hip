@@ -3,7 +3,9 @@
 // the practical ceiling the MLP kernels are measured against.  Prints TFLOP/s.
 // Then the unit-skip section: v_mfma_f32_32x32x1_2b_f32 (K = 1, two 32-point blocks) with
 // independent accumulators, as one dependent accumulate chain, with a wave-uniform "is this
-// unit +0 in every live lane" test and branch between instances, and with v_permlane32_swap
+// unit +0 in every live lane" test and branch between instances (8, 16 or 32 tests ahead of their
+// branches), with its weight operand read from LDS (a wide read issued ahead, or a 4-byte read in
+// front of the instruction), and with v_permlane32_swap
 // beside it; every figure as median [min, max] of 7 timed launches, next to the 16x16x4
 // stream timed the same way.  It also checks the instruction's D layout with exact integers.
 // build: hipcc --offload-arch=gfx950 -O3 mfma_peak.hip -o bin/mfma_peak
@@ -123,6 +125,74 @@ __global__ void k_u_skip(float *out, int iters, float b0, const float *av, unsig
     out[blockIdx.x * blockDim.x + threadIdx.x] = c[0] + c[31] + (float)(unsigned)(any >> 40);
 }
 
+// NT tests (8, 16 or 32: the units of one, two or four iterations of k_u_skip<1>) ahead of their
+// branches: what forming all of a layer's masks before its first branch costs in scalar registers
+template <int NT>
+__global__ void k_u_tests(float *out, int iters, float b0, const float *av, unsigned long long live) {
+    f32x32 c = f32x32{};
+    const int lane = threadIdx.x & 63;
+    unsigned a[8];
+    for (int k = 0; k < 8; ++k) a[k] = __float_as_uint(av[k * 64 + lane]);
+    float w = b0 + lane * 1e-9f;
+    asm volatile("" : "+v"(w));
+    for (int it = 0; it < iters; it += NT / 8) {
+        unsigned long long m[NT];
+#pragma unroll
+        for (int k = 0; k < NT; ++k) {
+            asm volatile("" : "+v"(a[k & 7]));
+            m[k] = __builtin_amdgcn_ballot_w64(a[k & 7] != 0u) & live;
+            asm volatile("" : "+s"(m[k]));
+        }
+#pragma unroll
+        for (int k = 0; k < NT; ++k)
+            if (m[k]) c = __builtin_amdgcn_mfma_f32_32x32x1f32(w, __uint_as_float(a[k & 7]), c, 0, 0, 0);
+    }
+    out[blockIdx.x * blockDim.x + threadIdx.x] = c[0] + c[31];
+}
+
+// one dependent chain of 8 units per iteration whose weight operand comes from LDS, [k >> 2][row 32][k & 3]
+// as the unit pack holds it.  MODE 0: one ds_read_b128 per four units, issued (inline asm) while
+// the four before run and waited for by hand, as the kernel does; 1: a 4-byte read directly in
+// front of each instance
+template <int MODE>
+__global__ void k_u_lds(float *out, int iters, float b0) {
+    __shared__ f32x4 wl[2][32];
+    const int lane = threadIdx.x & 63, row = lane & 31;
+    if (threadIdx.x < 64) wl[threadIdx.x >> 5][row] = f32x4{1.0f, 1.0f, 1.0f, 1.0f} * (1.0f + threadIdx.x * 1e-9f);
+    __syncthreads();
+    unsigned addr = (unsigned)(size_t)(const __attribute__((address_space(3))) f32x4 *)&wl[0][row];
+    asm volatile("" : "+v"(addr));
+    f32x32 c = f32x32{};
+    float b = b0;
+    asm volatile("" : "+v"(b));
+    if constexpr (MODE == 0) {
+        f32x4 w, n;
+        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(w) : "v"(addr));
+        for (int it = 0; it < iters; ++it) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                if (q == 0) asm volatile("ds_read_b128 %0, %1 offset:512" : "=&v"(n) : "v"(addr));
+                else asm volatile("ds_read_b128 %0, %1" : "=&v"(n) : "v"(addr));
+#pragma unroll
+                for (int i = 0; i < 4; ++i) c = __builtin_amdgcn_mfma_f32_32x32x1f32(w[i], b, c, 0, 0, 0);
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(n));
+                w = n;
+            }
+        }
+    } else {
+        for (int it = 0; it < iters; ++it) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                float w;
+                if (k < 4) asm volatile("ds_read_b32 %0, %1 offset:%2\n\ts_waitcnt lgkmcnt(0)" : "=&v"(w) : "v"(addr), "n"(4 * (k & 3)));
+                else asm volatile("ds_read_b32 %0, %1 offset:%2\n\ts_waitcnt lgkmcnt(0)" : "=&v"(w) : "v"(addr), "n"(512 + 4 * (k & 3)));
+                c = __builtin_amdgcn_mfma_f32_32x32x1f32(w, b, c, 0, 0, 0);
+            }
+        }
+    }
+    out[blockIdx.x * blockDim.x + threadIdx.x] = c[0] + c[31];
+}
+
 // one dependent chain with NS v_permlane32_swap (independent registers) after every instance
 template <int NS>
 __global__ void k_u_swap(float *out, int iters, float a0, float b0) {
@@ -232,6 +302,14 @@ static int unit_skip_section(int cus, float *out) {
                     [&] { hipLaunchKernelGGL(k_u_skip<1>, dim3(grid), dim3(256), 0, 0, out, iters, 1e-3f, av + 512, ~0ull); });
         ok &= timed("chain + test per unit, no branch, 8 of 8 issued", wps, fu, 157.3,
                     [&] { hipLaunchKernelGGL(k_u_skip<2>, dim3(grid), dim3(256), 0, 0, out, iters, 1e-3f, av, ~0ull); });
+        ok &= timed("chain, 16 tests first, then branch per unit, 5 of 8 issued", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u_tests<16>, dim3(grid), dim3(256), 0, 0, out, iters, 1e-3f, av + 512, ~0ull); });
+        ok &= timed("chain, 32 tests first, then branch per unit, 5 of 8 issued", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u_tests<32>, dim3(grid), dim3(256), 0, 0, out, iters, 1e-3f, av + 512, ~0ull); });
+        ok &= timed("chain, weights by ds_read_b128 four units ahead", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u_lds<0>, dim3(grid), dim3(256), 0, 0, out, iters, 1e-3f); });
+        ok &= timed("chain, weight by ds_read_b32 in front of each instance", wps, fu, 157.3,
+                    [&] { hipLaunchKernelGGL(k_u_lds<1>, dim3(grid), dim3(256), 0, 0, out, iters, 1e-3f); });
         ok &= timed("chain + 1 v_permlane32_swap per instance", wps, fu, 157.3,
                     [&] { hipLaunchKernelGGL(k_u_swap<1>, dim3(grid), dim3(256), 0, 0, out, iters, 1.0f, 1e-3f); });
         ok &= timed("chain + 2 v_permlane32_swap per instance", wps, fu, 157.3,
