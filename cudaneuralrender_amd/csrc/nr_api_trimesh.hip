@@ -1,0 +1,139 @@
+// nr_api_trimesh.hip -- the C ABI's triangle meshes (nr_trimesh_*).
+#include <climits>
+#include <cmath>
+#include <new>
+#include <vector>
+
+#include "nr_ctx.h"
+
+using namespace nr;
+
+// ---- triangle meshes (nr_trimesh_*; nr_trimesh_host.cpp, nr_trimesh.hip) ----
+// The hierarchy, the reordered triangles and the pseudonormal table are built on the host at create
+// time and live on the device; a query is one launch.
+struct nr_trimesh {
+    nr_ctx *owner = nullptr;
+    long nv = 0, nt = 0, nnodes = 0, ntl = 0;
+    int depth = 0, closed = 0;
+    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    float *d_nodes = nullptr, *d_tris = nullptr, *d_table = nullptr;
+    unsigned long long *d_stats = nullptr;
+    float *d_io = nullptr;        // staging of host points and results
+    size_t cap_io = 0;
+};
+
+extern "C" {
+
+int nr_trimesh_create(nr_ctx *owner, const float *vertices, long nv, const int32_t *triangles, long nt, int leaf,
+                      nr_trimesh **out) {
+    if (out) *out = nullptr;
+    if (!owner || !vertices || !triangles || !out) return set_err(owner, NR_E_INVALID, "nr_trimesh_create: NULL argument");
+    if (nv < 1 || nv > (long)INT32_MAX) return set_err(owner, NR_E_INVALID, "nr_trimesh_create: nv = %ld outside [1, 2^31)", nv);
+    if (nt < 1 || nt > (1l << 24)) return set_err(owner, NR_E_INVALID, "nr_trimesh_create: nt = %ld outside [1, 2^24]", nt);
+    if (leaf < 0 || leaf > 32) return set_err(owner, NR_E_INVALID, "nr_trimesh_create: leaf = %d outside 0..32", leaf);
+    if (!trimesh_indices_ok(triangles, nt, nv))
+        return set_err(owner, NR_E_INVALID, "nr_trimesh_create: a vertex index outside 0..%ld", nv - 1);
+    for (long i = 0; i < 3 * nv; ++i)
+        if (!std::isfinite(vertices[i])) return set_err(owner, NR_E_INVALID, "nr_trimesh_create: vertex %ld is not finite", i / 3);
+    nr_trimesh *m = new (std::nothrow) nr_trimesh();
+    if (!m) return set_err(owner, NR_E_NOMEM, "out of host memory");
+    m->owner = owner;
+    m->nv = nv; m->nt = nt;
+    std::vector<float> table((size_t)nt * 21);
+    trimesh_normals(vertices, nv, triangles, nt, table.data(), &m->closed);
+    TriBvh H;
+    if (!trimesh_build(vertices, nv, triangles, nt, leaf > 0 ? leaf : TRIMESH_LEAF_DEFAULT, table.data(), H)) {
+        delete m;
+        return set_err(owner, NR_E_INVALID, "nr_trimesh_create: a hierarchy of %d levels (the walk's stack holds %d)", H.depth, TRIMESH_STACK);
+    }
+    m->nnodes = H.nnodes; m->ntl = H.ntl; m->depth = H.depth;
+    for (int a = 0; a < 3; ++a) { m->lo[a] = H.lo[a]; m->hi[a] = H.hi[a]; }
+    hipError_t e = hipSetDevice(owner->device);
+    hipStream_t s = e == hipSuccess ? cur_stream(owner) : nullptr;
+    if (e == hipSuccess && owner->use_own && !owner->own_stream) { delete m; return NR_E_HIP; }
+    if (e == hipSuccess) e = hipMalloc(&m->d_nodes, H.nodes.size() * 4);
+    if (e == hipSuccess) e = hipMalloc(&m->d_tris, H.tris.size() * 4);
+    if (e == hipSuccess) e = hipMalloc(&m->d_table, table.size() * 4);
+    if (e == hipSuccess) e = hipMalloc(&m->d_stats, 128);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->d_nodes, H.nodes.data(), H.nodes.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->d_tris, H.tris.data(), H.tris.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // (the sources are locals)
+    if (e != hipSuccess) {
+        const bool nomem = e == hipErrorOutOfMemory;
+        dfree(m->d_nodes); dfree(m->d_tris); dfree(m->d_table); dfree(m->d_stats);
+        delete m;
+        return set_err(owner, nomem ? NR_E_NOMEM : NR_E_HIP, "nr_trimesh_create: %s", hipGetErrorString(e));
+    }
+    *out = m;
+    return NR_OK;
+}
+
+int nr_trimesh_destroy(nr_trimesh *m) {
+    if (!m) return NR_OK;
+    nr_ctx *c = m->owner;
+    (void)hipSetDevice(c->device);
+    if (!(c->use_own && !c->own_stream)) (void)hipStreamSynchronize(c->stream);
+    dfree(m->d_nodes); dfree(m->d_tris); dfree(m->d_table); dfree(m->d_stats); dfree(m->d_io);
+    delete m;
+    return NR_OK;
+}
+
+int nr_trimesh_info(const nr_trimesh *m, long *nv, long *nt, long *nodes, int *depth, float lo[3], float hi[3], int *closed) {
+    if (!m) return set_err(nullptr, NR_E_INVALID, "nr_trimesh_info: mesh is NULL");
+    if (nv) *nv = m->nv;
+    if (nt) *nt = m->nt;
+    if (nodes) *nodes = m->nnodes;
+    if (depth) *depth = m->depth;
+    for (int a = 0; a < 3; ++a) {
+        if (lo) lo[a] = m->lo[a];
+        if (hi) hi[a] = m->hi[a];
+    }
+    if (closed) *closed = m->closed;
+    return NR_OK;
+}
+
+int nr_trimesh_distance(nr_trimesh *m, const float *X, long n, float *sdf, float *closest, int32_t *tri, int32_t *feature,
+                        int flags, int loc, nr_stats *stats) {
+    if (!m) return set_err(nullptr, NR_E_INVALID, "nr_trimesh_distance: mesh is NULL");
+    nr_ctx *c = m->owner;
+    if (!X) return set_err(c, NR_E_INVALID, "nr_trimesh_distance: X is NULL");
+    if (n < 1 || n > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_trimesh_distance: n = %ld outside [1, 2^30]", n);
+    if (flags & ~NR_TRIMESH_BRUTE) return set_err(c, NR_E_INVALID, "nr_trimesh_distance: unknown flag bits %#x", flags);
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const size_t N = (size_t)n;
+    TriMeshArgs A{};
+    A.X = X; A.n = n;
+    A.nodes = m->d_nodes; A.tris = m->d_tris; A.table = m->d_table;
+    A.nnodes = (int)m->nnodes; A.ntl = (int)m->ntl;
+    A.brute = (flags & NR_TRIMESH_BRUTE) != 0;
+    A.sdf = sdf; A.closest = closest; A.tri = tri; A.feature = feature;
+    A.stats = m->d_stats;
+    // staged: the points, then every output the caller asked for
+    Staging io(loc);
+    io.in(A.X, 3 * N);
+    io.out(A.sdf, N); io.out(A.closest, 3 * N); io.out(A.tri, N); io.out(A.feature, N);
+    int rc;
+    if ((rc = io.begin(c, m->d_io, m->cap_io, s)) != NR_OK) return rc;
+    // a grid-stride over chunks of 64 points: at most 8 four-wave workgroups per CU
+    const size_t chunks = (N + 63) / 64;
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((chunks + 3) / 4, (size_t)num_cus(c->device) * 8));
+    nr_stats st{};
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, hipMemsetAsync(m->d_stats, 0, 8, s));
+    HIPCHK(c, launch_trimesh_distance(A, grid, s));
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if ((rc = io.end(c, s)) != NR_OK) return rc;
+    unsigned long long evals = 0;
+    if (stats) HIPCHK(c, hipMemcpyAsync(&evals, m->d_stats, 8, hipMemcpyDeviceToHost, s));
+    rc = end_timed(c, stats != nullptr, loc, s, &st.ms_total);
+    if (rc != NR_OK || !stats) return rc;
+    st.ray_steps = (uint64_t)n;
+    st.shade_evals = evals;
+    st.launches = 2;  // the counter's memset and k_trimesh_distance
+    *stats = st;
+    return NR_OK;
+}
+
+}  // extern "C"

@@ -31,8 +31,7 @@
 #include <thread>
 #include <vector>
 
-#include "nr_internal.h"
-#include "nr_kernels.h"
+#include "nr_ctx.h"
 
 struct nr_group {
     int n = 0;
@@ -109,7 +108,7 @@ int nr_group_create_ex(nr_ctx *const *ctxs, int n, int flags, nr_group **out) {
                 release(g);
                 return nr::report_error(NR_E_INVALID, "nr_group_create: context %d appears twice", r);
             }
-        const int d = nr::ctx_device(ctxs[r]);
+        const int d = ctxs[r]->device;
         if (!(flags & NR_GROUP_COPY) && std::find(g->dev.begin(), g->dev.end(), d) != g->dev.end()) {
             release(g);
             return nr::report_error(NR_E_INVALID, "nr_group_create: two contexts on device %d (one GPU per rank "
@@ -228,7 +227,7 @@ int nr_group_render_batch(nr_group *g, const nr_frame *frames, int nframes, int 
             msg[r] = "hipSetDevice failed";
             return;
         }
-        const hipStream_t rs = (hipStream_t)nr::ctx_stream(g->ctx[r]);
+        const hipStream_t rs = nr::cur_stream(g->ctx[r]);
         if (g->calls >= 2 && hipStreamWaitEvent(rs, g->sent[b][r], 0) != hipSuccess) {
             rc[r] = NR_E_HIP;
             msg[r] = "hipStreamWaitEvent failed";

@@ -273,10 +273,6 @@ struct TriBvh {
 };
 bool trimesh_build(const float *V, long nv, const int32_t *T, long nt, int leaf, const float *table, TriBvh &out);
 
-// ---- context internals for nr_group.hip (nr_api.hip) ----
-int ctx_device(const nr_ctx *c);
-void *ctx_stream(nr_ctx *c);  // the hipStream_t the context's work runs on (creates its own stream if selected)
-
 // ---- camera (nr_pack.cpp; the C ABI's nr_camera) ----
 void camera_matrices(float rx, float ry, float zoom, float tx, float ty, float inv_view[12], float normal[16]);
 void camera_matrices_eigen(float rx, float ry, float zoom, float tx, float ty, float inv_view[12], float normal[16]);

@@ -1332,7 +1332,7 @@ static hipError_t launch_trace_k(const RenderArgs &A, const MlpArgs &M, const Tr
     if constexpr (LOWP && !PROBE) {
         if constexpr (!STAMPS) {
             if (M.x3n && T.eg_tau > 0.0f) {
-                // the grid is at most NR_TRACE_BPC_EG 4-wave workgroups per CU (nr_api.hip trace_bpc):
+                // the grid is at most NR_TRACE_BPC_EG 4-wave workgroups per CU (nr_api_render.hip trace_bpc):
                 // as NR_EG_WAVES-wave workgroups, one per CU, with the fp32x3 pack in their LDS --
                 // when the two packs fit beside the instance's static LDS (networks of up to 9 hidden
                 // layers), else as round 5's 4-wave workgroups reading the pack from global memory
