@@ -51,7 +51,7 @@ EXPORTS = [
     "nr_compose_render_lit",
     "nr_fit_create", "nr_fit_destroy", "nr_fit_num_params", "nr_fit_gradient", "nr_fit_run", "nr_fit_weights",
     "nr_obj_load", "nr_trimesh_normals", "nr_trimesh_create", "nr_trimesh_destroy", "nr_trimesh_info",
-    "nr_trimesh_distance",
+    "nr_trimesh_distance", "nr_mesh_hierarchy", "nr_mesh_winding",
 ]
 # nr_trimesh_distance: flags, and the feature codes of its `feature` output
 NR_TRIMESH_BRUTE = 1
@@ -301,6 +301,9 @@ def lib():
         "nr_trimesh_destroy": (I, [P]),
         "nr_trimesh_info": (I, [P, ctypes.POINTER(L64), ctypes.POINTER(L64), ctypes.POINTER(L64), IP, FP, FP, IP]),
         "nr_trimesh_distance": (I, [P, P, L64, P, P, P, P, I, I, ctypes.POINTER(NRStats)]),
+        "nr_mesh_hierarchy": (I, [P, L64, P, L64, I, ctypes.POINTER(FP), ctypes.POINTER(L64), ctypes.POINTER(IP),
+                                  ctypes.POINTER(L64), ctypes.POINTER(FP), IP]),
+        "nr_mesh_winding": (I, [P, P, L64, ctypes.c_float, P, P, I, I, ctypes.POINTER(NRStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

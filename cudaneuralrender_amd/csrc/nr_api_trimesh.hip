@@ -8,15 +8,16 @@
 
 using namespace nr;
 
-// ---- triangle meshes (nr_trimesh_*; nr_trimesh_host.cpp, nr_trimesh.hip) ----
-// The hierarchy, the reordered triangles and the pseudonormal table are built on the host at create
-// time and live on the device; a query is one launch.
+// ---- triangle meshes (nr_trimesh_*; nr_trimesh_host.cpp, nr_trimesh.hip, nr_winding.hip) ----
+// The hierarchy with its moments, the reordered triangles and the pseudonormal table are built on
+// the host at create time and live on the device; a distance query is one launch, a winding query
+// one, or two with the sdf output.
 struct nr_trimesh {
     nr_ctx *owner = nullptr;
     long nv = 0, nt = 0, nnodes = 0, ntl = 0;
     int depth = 0, closed = 0;
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    float *d_nodes = nullptr, *d_tris = nullptr, *d_table = nullptr;
+    float *d_nodes = nullptr, *d_tris = nullptr, *d_table = nullptr, *d_moments = nullptr;
     unsigned long long *d_stats = nullptr;
     float *d_io = nullptr;        // staging of host points and results
     size_t cap_io = 0;
@@ -54,14 +55,16 @@ int nr_trimesh_create(nr_ctx *owner, const float *vertices, long nv, const int32
     if (e == hipSuccess) e = hipMalloc(&m->d_nodes, H.nodes.size() * 4);
     if (e == hipSuccess) e = hipMalloc(&m->d_tris, H.tris.size() * 4);
     if (e == hipSuccess) e = hipMalloc(&m->d_table, table.size() * 4);
+    if (e == hipSuccess) e = hipMalloc(&m->d_moments, H.moments.size() * 4);
     if (e == hipSuccess) e = hipMalloc(&m->d_stats, 128);
     if (e == hipSuccess) e = hipMemcpyAsync(m->d_nodes, H.nodes.data(), H.nodes.size() * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(m->d_tris, H.tris.data(), H.tris.size() * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(m->d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->d_moments, H.moments.data(), H.moments.size() * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);  // (the sources are locals)
     if (e != hipSuccess) {
         const bool nomem = e == hipErrorOutOfMemory;
-        dfree(m->d_nodes); dfree(m->d_tris); dfree(m->d_table); dfree(m->d_stats);
+        dfree(m->d_nodes); dfree(m->d_tris); dfree(m->d_table); dfree(m->d_moments); dfree(m->d_stats);
         delete m;
         return set_err(owner, nomem ? NR_E_NOMEM : NR_E_HIP, "nr_trimesh_create: %s", hipGetErrorString(e));
     }
@@ -74,7 +77,7 @@ int nr_trimesh_destroy(nr_trimesh *m) {
     nr_ctx *c = m->owner;
     (void)hipSetDevice(c->device);
     if (!(c->use_own && !c->own_stream)) (void)hipStreamSynchronize(c->stream);
-    dfree(m->d_nodes); dfree(m->d_tris); dfree(m->d_table); dfree(m->d_stats); dfree(m->d_io);
+    dfree(m->d_nodes); dfree(m->d_tris); dfree(m->d_table); dfree(m->d_moments); dfree(m->d_stats); dfree(m->d_io);
     delete m;
     return NR_OK;
 }
@@ -132,6 +135,61 @@ int nr_trimesh_distance(nr_trimesh *m, const float *X, long n, float *sdf, float
     st.ray_steps = (uint64_t)n;
     st.shade_evals = evals;
     st.launches = 2;  // the counter's memset and k_trimesh_distance
+    *stats = st;
+    return NR_OK;
+}
+
+int nr_mesh_winding(nr_trimesh *m, const float *X, long n, float beta, float *winding, float *sdf, int flags, int loc,
+                    nr_stats *stats) {
+    if (!m) return set_err(nullptr, NR_E_INVALID, "nr_mesh_winding: mesh is NULL");
+    nr_ctx *c = m->owner;
+    if (!X) return set_err(c, NR_E_INVALID, "nr_mesh_winding: X is NULL");
+    if (!winding && !sdf) return set_err(c, NR_E_INVALID, "nr_mesh_winding: winding and sdf are both NULL");
+    if (n < 1 || n > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_mesh_winding: n = %ld outside [1, 2^30]", n);
+    if (!std::isfinite(beta) || beta < 0.0f) return set_err(c, NR_E_INVALID, "nr_mesh_winding: beta = %g is negative or not finite", (double)beta);
+    if (flags & ~NR_TRIMESH_BRUTE) return set_err(c, NR_E_INVALID, "nr_mesh_winding: unknown flag bits %#x", flags);
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const size_t N = (size_t)n;
+    TriWindArgs A{};
+    A.X = X; A.n = n;
+    A.nodes = m->d_nodes; A.tris = m->d_tris; A.moments = m->d_moments;
+    A.nnodes = (int)m->nnodes; A.ntl = (int)m->ntl;
+    A.brute = (flags & NR_TRIMESH_BRUTE) != 0;
+    A.beta = beta == 0.0f ? 2.0f : beta;
+    A.winding = winding; A.sdf = sdf;
+    A.stats = m->d_stats;
+    Staging io(loc);
+    io.in(A.X, 3 * N);
+    io.out(A.winding, N); io.out(A.sdf, N);
+    int rc;
+    if ((rc = io.begin(c, m->d_io, m->cap_io, s)) != NR_OK) return rc;
+    const size_t chunks = (N + 63) / 64;
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((chunks + 3) / 4, (size_t)num_cus(c->device) * 8));
+    nr_stats st{};
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, hipMemsetAsync(m->d_stats, 0, 8, s));
+    if (A.sdf) {
+        // the magnitude first, by the distance call's own launch; k_trimesh_winding then signs it in place
+        TriMeshArgs D{};
+        D.X = A.X; D.n = n;
+        D.nodes = m->d_nodes; D.tris = m->d_tris; D.table = m->d_table;
+        D.nnodes = A.nnodes; D.ntl = A.ntl;
+        D.brute = A.brute;
+        D.sdf = A.sdf;
+        D.stats = m->d_stats;
+        HIPCHK(c, launch_trimesh_distance(D, grid, s));
+    }
+    HIPCHK(c, launch_trimesh_winding(A, grid, s));
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if ((rc = io.end(c, s)) != NR_OK) return rc;
+    unsigned long long evals = 0;
+    if (stats) HIPCHK(c, hipMemcpyAsync(&evals, m->d_stats, 8, hipMemcpyDeviceToHost, s));
+    rc = end_timed(c, stats != nullptr, loc, s, &st.ms_total);
+    if (rc != NR_OK || !stats) return rc;
+    st.ray_steps = (uint64_t)n;
+    st.shade_evals = evals;
+    st.launches = A.sdf ? 3 : 2;  // the counter's memset, k_trimesh_distance for sdf, k_trimesh_winding
     *stats = st;
     return NR_OK;
 }

@@ -258,14 +258,16 @@ void trimesh_normals(const float *V, long nv, const int32_t *T, long nt, float *
 //          triangles [first, first + count) of `tris` (word 7 <= 0) or an inner node's children (word 7
 //          > 0; the root is node 0, so no child is).  Preorder: a node, its left subtree, its right one.
 //   tris   12 words each, leaf by leaf: a.xyz, original index, b.xyz, 0, c.xyz, 0
+//   moments 16 words each, node by node (k_trimesh_winding's far field; include/neural_render.h):
+//          centre.xyz, R2, N.xyz, 0, Sxx, Syy, Szz, Sxy, Sxz, Syz, 0, 0
 // Boxes are inflated by slack = 2^-TRIMESH_SLACK_SHIFT (largest |coordinate| + largest axis extent)
 // and rounded outward.  False when the depth exceeds ceil(log2 ntl) + 1 or TRIMESH_STACK (the wave's
-// stack in k_trimesh_distance holds one pending child per level).
+// stack in k_trimesh_distance and k_trimesh_winding holds one pending child per level).
 constexpr int TRIMESH_SLACK_SHIFT = 18;
 constexpr int TRIMESH_STACK = 32;
 constexpr int TRIMESH_LEAF_DEFAULT = 8;
 struct TriBvh {
-    std::vector<float> nodes, tris;
+    std::vector<float> nodes, tris, moments;
     long nnodes = 0, ntl = 0;
     int depth = 0;
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // the vertices' bound, not inflated

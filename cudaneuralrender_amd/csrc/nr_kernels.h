@@ -319,6 +319,22 @@ struct TriMeshArgs {
 };
 hipError_t launch_trimesh_distance(const TriMeshArgs &A, int grid, hipStream_t st);  // 4-wave workgroups
 
+// The generalized winding number of a triangle mesh (nr_winding.hip k_trimesh_winding;
+// nr_mesh_winding): every point writes its slot of the outputs that are not NULL.
+struct TriWindArgs {
+    const float *X;               // [n][3]
+    long n;                       // 1 .. 2^30
+    const float *nodes, *tris;    // [nnodes][8], [ntl][12]
+    const float *moments;         // [nnodes][16]
+    int nnodes, ntl;
+    int brute;                    // every triangle of tris in order, no expansion
+    float beta;                   // a node is far iff |centre - p|^2 > beta^2 R2
+    float *winding;               // [n]
+    float *sdf;                   // [n]: k_trimesh_distance's result on entry, signed by the winding number on exit
+    unsigned long long *stats;    // [0] += solid angles and expansions evaluated (not zeroed here)
+};
+hipError_t launch_trimesh_winding(const TriWindArgs &A, int grid, hipStream_t st);  // 4-wave workgroups
+
 // Composed scenes (nr_compose.hip; nr_compose_*): the distinct fp32 packs back to back in one device
 // buffer (staged into dynamic LDS in that order), the parts, and the queried rays or points.  The
 // struct travels in the kernarg segment: the part loop is wave-uniform and reads it with scalar loads.

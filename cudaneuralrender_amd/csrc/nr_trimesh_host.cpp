@@ -1,7 +1,9 @@
-// nr_trimesh_host.cpp -- the host side of the triangle-mesh distance query (nr_trimesh_*): the OBJ reader
+// nr_trimesh_host.cpp -- the host side of the triangle-mesh queries (nr_trimesh_*): the OBJ reader
 // (nr_obj_load), the pseudonormal table (nr_trimesh_normals) and the hierarchy k_trimesh_distance
-// walks (trimesh_build).  No GPU and no HIP here: tests/cpp/trimesh_sanitize.cpp links this file
-// alone.  The contract is in include/neural_render.h; tests/trimesh_ref.py restates it in numpy.
+// and k_trimesh_winding walk, with the far-field moments of every node (trimesh_build;
+// nr_mesh_hierarchy returns it).  No GPU and no HIP here: tests/cpp/trimesh_sanitize.cpp links
+// this file alone.  The contract is in include/neural_render.h; tests/trimesh_ref.py and
+// tests/winding_ref.py restate it in numpy.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -287,6 +289,68 @@ struct Builder {
         return me;
     }
 };
+
+// The far-field record of every node of H (the header's "moments"): sums in double over the node's
+// triangles in position order, each entry rounded to f32 once.  The centre is rounded first and S and
+// R2 are taken about the rounded centre, the one k_trimesh_winding expands about.
+void trimesh_moments(TriBvh &H) {
+    const long nn = H.nnodes, ntl = H.ntl;
+    H.moments.assign((size_t)nn * 16, 0.0f);
+    std::vector<double> q((size_t)ntl * 7);  // per position: A.xyz, |A|, x.xyz
+    for (long k = 0; k < ntl; ++k) {
+        const float *t = H.tris.data() + (size_t)k * 12;
+        const D3 A = cross(sub(t + 4, t), sub(t + 8, t));
+        double *o = q.data() + (size_t)k * 7;
+        o[0] = 0.5 * A.x; o[1] = 0.5 * A.y; o[2] = 0.5 * A.z;
+        o[3] = std::sqrt((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]);
+        for (int a = 0; a < 3; ++a) o[4 + a] = (((double)t[a] + (double)t[4 + a]) + (double)t[8 + a]) / 3.0;
+    }
+    // a node's triangles [first, first + count): children follow their parent in preorder
+    std::vector<int32_t> first((size_t)nn), count((size_t)nn);
+    for (long i = nn - 1; i >= 0; --i) {
+        int32_t w3, w7;
+        memcpy(&w3, &H.nodes[(size_t)i * 8 + 3], 4);
+        memcpy(&w7, &H.nodes[(size_t)i * 8 + 7], 4);
+        if (w7 <= 0) { first[(size_t)i] = w3; count[(size_t)i] = -w7; }
+        else { first[(size_t)i] = first[(size_t)w3]; count[(size_t)i] = count[(size_t)w3] + count[(size_t)w7]; }
+    }
+    for (long i = 0; i < nn; ++i) {
+        const long k0 = first[(size_t)i], k1 = k0 + count[(size_t)i];
+        if (k1 == k0) continue;
+        double sa = 0.0, sx[3] = {0.0, 0.0, 0.0}, mx[3] = {0.0, 0.0, 0.0}, N[3] = {0.0, 0.0, 0.0};
+        for (long k = k0; k < k1; ++k) {
+            const double *o = q.data() + (size_t)k * 7;
+            sa += o[3];
+            for (int a = 0; a < 3; ++a) { sx[a] += o[3] * o[4 + a]; mx[a] += o[4 + a]; N[a] += o[a]; }
+        }
+        float *rec = H.moments.data() + (size_t)i * 16;
+        double c[3];
+        for (int a = 0; a < 3; ++a) {
+            rec[a] = (float)(sa > 0.0 ? sx[a] / sa : mx[a] / (double)(k1 - k0));
+            c[a] = (double)rec[a];
+            rec[4 + a] = (float)N[a];
+        }
+        double M[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, r2 = 0.0;
+        for (long k = k0; k < k1; ++k) {
+            const double *o = q.data() + (size_t)k * 7;
+            const double d[3] = {o[4] - c[0], o[5] - c[1], o[6] - c[2]};
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3; ++b) M[a][b] += o[a] * d[b];
+            const float *t = H.tris.data() + (size_t)k * 12;
+            for (int v = 0; v < 3; ++v) {
+                const double e0 = (double)t[4 * v] - c[0], e1 = (double)t[4 * v + 1] - c[1], e2 = (double)t[4 * v + 2] - c[2];
+                r2 = std::max(r2, (e0 * e0 + e1 * e1) + e2 * e2);
+            }
+        }
+        float R2 = (float)r2;
+        if ((double)R2 < r2) R2 = std::nextafterf(R2, INFINITY);
+        rec[3] = R2;
+        rec[8] = (float)M[0][0]; rec[9] = (float)M[1][1]; rec[10] = (float)M[2][2];
+        rec[11] = (float)(0.5 * (M[0][1] + M[1][0]));
+        rec[12] = (float)(0.5 * (M[0][2] + M[2][0]));
+        rec[13] = (float)(0.5 * (M[1][2] + M[2][1]));
+    }
+}
 }  // namespace
 
 bool trimesh_build(const float *V, long nv, const int32_t *T, long nt, int leaf, const float *table, TriBvh &out) {
@@ -330,6 +394,7 @@ bool trimesh_build(const float *V, long nv, const int32_t *T, long nt, int leaf,
             for (int a = 0; a < 3; ++a) o[4 * c + a] = V[3 * (size_t)T[3 * t + c] + a];
         memcpy(o + 3, &t, 4);
     }
+    trimesh_moments(out);
     // ceil(log2 ntl) + 1 levels at most
     int bound = 1;
     while ((1l << (bound - 1)) < std::max(ntl, 1l)) ++bound;
@@ -368,6 +433,39 @@ int nr_trimesh_normals(const float *vertices, long nv, const int32_t *triangles,
     if (nv < 1 || nt < 1 || nt > (1l << 24)) return nr::report_error(NR_E_INVALID, "nr_trimesh_normals: nv = %ld or nt = %ld out of range", nv, nt);
     if (!nr::trimesh_indices_ok(triangles, nt, nv)) return nr::report_error(NR_E_INVALID, "nr_trimesh_normals: a vertex index outside 0..%ld", nv - 1);
     nr::trimesh_normals(vertices, nv, triangles, nt, table, closed);
+    return NR_OK;
+}
+
+int nr_mesh_hierarchy(const float *vertices, long nv, const int32_t *triangles, long nt, int leaf, float **nodes,
+                      long *nnodes, int32_t **order, long *ntl, float **moments, int *depth) {
+    if (nodes) *nodes = nullptr;
+    if (order) *order = nullptr;
+    if (moments) *moments = nullptr;
+    if (nnodes) *nnodes = 0;
+    if (ntl) *ntl = 0;
+    if (depth) *depth = 0;
+    if (!vertices || !triangles || !nodes || !nnodes || !order || !ntl || !moments || !depth)
+        return nr::report_error(NR_E_INVALID, "nr_mesh_hierarchy: NULL argument");
+    if (nv < 1 || nv > (long)std::numeric_limits<int32_t>::max() || nt < 1 || nt > (1l << 24))
+        return nr::report_error(NR_E_INVALID, "nr_mesh_hierarchy: nv = %ld or nt = %ld out of range", nv, nt);
+    if (leaf < 0 || leaf > 32) return nr::report_error(NR_E_INVALID, "nr_mesh_hierarchy: leaf = %d outside 0..32", leaf);
+    if (!nr::trimesh_indices_ok(triangles, nt, nv)) return nr::report_error(NR_E_INVALID, "nr_mesh_hierarchy: a vertex index outside 0..%ld", nv - 1);
+    for (long i = 0; i < 3 * nv; ++i)
+        if (!std::isfinite(vertices[i])) return nr::report_error(NR_E_INVALID, "nr_mesh_hierarchy: vertex %ld is not finite", i / 3);
+    std::vector<float> table((size_t)nt * 21);
+    nr::trimesh_normals(vertices, nv, triangles, nt, table.data(), nullptr);
+    nr::TriBvh H;
+    if (!nr::trimesh_build(vertices, nv, triangles, nt, leaf > 0 ? leaf : nr::TRIMESH_LEAF_DEFAULT, table.data(), H))
+        return nr::report_error(NR_E_INVALID, "nr_mesh_hierarchy: a hierarchy of %d levels (the walk's stack holds %d)", H.depth, nr::TRIMESH_STACK);
+    float *n = (float *)malloc(H.nodes.size() * 4), *m = (float *)malloc(H.moments.size() * 4);
+    int32_t *o = (int32_t *)malloc(std::max<size_t>((size_t)H.ntl, 1) * 4);
+    if (!n || !m || !o) { free(n); free(m); free(o); return nr::report_error(NR_E_NOMEM, "nr_mesh_hierarchy: out of host memory"); }
+    memcpy(n, H.nodes.data(), H.nodes.size() * 4);
+    memcpy(m, H.moments.data(), H.moments.size() * 4);
+    for (long k = 0; k < H.ntl; ++k) memcpy(o + k, &H.tris[(size_t)k * 12 + 3], 4);
+    *nodes = n; *nnodes = H.nnodes;
+    *order = o; *ntl = H.ntl;
+    *moments = m; *depth = H.depth;
     return NR_OK;
 }
 

@@ -136,6 +136,27 @@ def trimesh_normals(vertices, triangles):
     return table, bool(closed.value)
 
 
+def trimesh_hierarchy(vertices, triangles, leaf=0):
+    """nr_mesh_hierarchy: (nodes [nnodes, 8] float32, order [ntl] int32, moments [nnodes, 16] float32,
+    depth) -- the tree nr_trimesh_create builds and uploads, without a GPU.  Words 3 and 7 of a node
+    are int32 (nodes.view(np.int32)): first | -count of a leaf, left | right child of an inner node;
+    order is the original index of the live triangle at each position."""
+    V, T = _mesh_arrays(vertices, triangles)
+    L = lib()
+    np_, mp, op = _FP(), _FP(), ctypes.POINTER(ctypes.c_int)()
+    nn, ntl, depth = ctypes.c_long(0), ctypes.c_long(0), ctypes.c_int(0)
+    check(L.nr_mesh_hierarchy(V.ctypes.data, V.shape[0], T.ctypes.data, T.shape[0], int(leaf), ctypes.byref(np_),
+                              ctypes.byref(nn), ctypes.byref(op), ctypes.byref(ntl), ctypes.byref(mp), ctypes.byref(depth)))
+    try:
+        nodes = np.ctypeslib.as_array(np_, shape=(nn.value, 8)).copy()
+        moments = np.ctypeslib.as_array(mp, shape=(nn.value, 16)).copy()
+        order = np.ctypeslib.as_array(op, shape=(ntl.value,)).copy() if ntl.value else np.zeros(0, np.int32)
+    finally:
+        for q in (np_, mp, op):
+            L.nr_free(ctypes.cast(q, ctypes.c_void_p))
+    return nodes.astype(np.float32, copy=False), order.astype(np.int32, copy=False), moments.astype(np.float32, copy=False), depth.value
+
+
 def _lattice(origin, step, dims):
     """(origin, step, dims) as the C arrays of the lattice calls"""
     o = np.ascontiguousarray(origin, np.float32).reshape(3)
@@ -1409,4 +1430,34 @@ class TriMesh:
         st = NRStats()
         self._chk(self._L.nr_trimesh_distance(self._m, vp[0], int(n), *vp[1:], NR_TRIMESH_BRUTE if brute else 0, NR_DEVICE,
                                               ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
+    def winding(self, X, beta=0.0, sdf=False, brute=False, with_stats=False):
+        """nr_mesh_winding on a host array X [n, 3]: {"winding" [n][, "sdf" [n]]} -- the generalized
+        winding number (1 inside a closed mesh that winds outward, 0 outside; w >= 0.5 is the inside
+        test of a mesh that is open or overlaps itself) and, with sdf, nr_trimesh_distance's magnitude
+        signed by that test.  beta: a node counts as far beyond beta radii, 0 = 2.0.  brute: every
+        triangle, no expansion.  Neighbours in space should be neighbours in X."""
+        X = np.ascontiguousarray(X, np.float32)
+        if X.ndim != 2 or X.shape[1] != 3:
+            raise ValueError(f"X must be [n, 3], got {X.shape}")
+        n = X.shape[0]
+        out = {"winding": np.zeros(n, np.float32)}
+        if sdf:
+            out["sdf"] = np.zeros(n, np.float32)
+        st = NRStats()
+        self._chk(self._L.nr_mesh_winding(self._m, X.ctypes.data, n, float(beta), out["winding"].ctypes.data,
+                                          out["sdf"].ctypes.data if sdf else None, NR_TRIMESH_BRUTE if brute else 0,
+                                          NR_HOST, ctypes.byref(st) if with_stats else None))
+        return (out, st.as_dict()) if with_stats else out
+
+    def winding_device(self, x_ptr, n, winding_ptr=0, sdf_ptr=0, beta=0.0, brute=False, with_stats=False):
+        """nr_mesh_winding on device buffers (float32 X [n, 3], winding [n], sdf [n]); 0 or None = that
+        output is not wanted, one of the two has to be.  Runs on the renderer's stream and, without
+        stats, returns without waiting."""
+        vp = [ctypes.c_void_p(p) if p else None for p in (x_ptr, winding_ptr, sdf_ptr)]
+        st = NRStats()
+        self._chk(self._L.nr_mesh_winding(self._m, vp[0], int(n), float(beta), vp[1], vp[2],
+                                          NR_TRIMESH_BRUTE if brute else 0, NR_DEVICE,
+                                          ctypes.byref(st) if with_stats else None))
         return st.as_dict() if with_stats else None

@@ -729,7 +729,8 @@ int nr_fit_weights(nr_fit *f, float *params /*[P], host*/, long *step);
  *     d = sqrtf(d2), correctly rounded.
  *  3. Sign: s = dot(p - q, N[tri][feature]); sdf = s < 0 ? -d : d.  With the library's meshes
  *     ((b - a) x (c - a) points outward: step 4 of nr_mesh_grid) inside is negative.  The sign means
- *     something only for a closed mesh (closed = 1); otherwise it is computed all the same.
+ *     something only for a closed mesh (closed = 1); otherwise it is computed all the same
+ *     (nr_mesh_winding, below, signs the distance to a mesh that is not closed).
  *  4. A point with a non-finite coordinate, or a mesh of zero-area triangles only, gives sdf = closest =
  *     the quiet NaN 0x7fc00000 and tri = feature = -1.
  * The hierarchy (built by nr_trimesh_create on the host): a binary tree over the triangles' boxes,
@@ -755,8 +756,81 @@ int nr_fit_weights(nr_fit *f, float *params /*[P], host*/, long *step);
  * an index outside 0..nv - 1; a vertex that is not finite; leaf outside 0..32; n < 1; n > 2^30; a flag
  * bit other than NR_TRIMESH_BRUTE), NR_E_IO and NR_E_FORMAT (nr_obj_load), NR_E_HIP, NR_E_NOMEM.
  * Memory on the device until nr_trimesh_destroy: 132 bytes per triangle (48: the reordered corners
- * and index; 84: the table) and 32 bytes per node (at most 2 ceil(nt / ceil(leaf / 2)) nodes), and for
- * NR_HOST callers staging of the points' and outputs' size. */
+ * and index; 84: the table) and 96 bytes per node (32: the box and the links; 64: the moments of
+ * nr_mesh_winding; at most 2 ceil(nt / ceil(leaf / 2)) nodes), and for NR_HOST callers staging of
+ * the points' and outputs' size.
+ *
+ * nr_mesh_winding: the generalized winding number (Jacobson et al. 2013) w of the mesh at each
+ * point -- the signed solid angles of all triangles seen from the point, summed, over 4 pi -- through
+ * the hierarchy with far nodes replaced by an expansion of their moments (Barill et al. 2018).  For a
+ * closed mesh whose triangles wind outward w is 1 inside and 0 outside; for an open, overlapping or
+ * nested mesh it varies smoothly and w >= 0.5 is the inside test.  Unlike the distance the result
+ * depends on the hierarchy and on the order of the sum, so both are part of the contract
+ * (tests/winding_ref.py restates it; nr_mesh_hierarchy returns the tree).  Both calls belong to the
+ * nr_trimesh object above: nr_mesh_winding queries one, nr_mesh_hierarchy returns what its
+ * creation builds.
+ *
+ * The hierarchy's layout (nr_mesh_hierarchy, host only, no device: exactly what nr_trimesh_create
+ * uploads, the caller's to nr_free).  The live triangles -- those whose face entry is not (0, 0, 0) --
+ * are reordered: order [ntl] is the original index of the triangle at each position.  nodes
+ * [nnodes][8] 32-bit words, the root first, in preorder (a node, its left subtree, its right one):
+ * words 0..2 and 4..6 the grown box (f32), word 3 | word 7 (int32) = first | -count of a leaf's
+ * triangles, positions [first, first + count), or left | right child of an inner node (word 7 > 0).
+ * A node's triangles are contiguous positions.  moments [nnodes][16] f32 per node:
+ *     c.xyz, R2, N.xyz, 0, Sxx, Syy, Szz, Sxy, Sxz, Syz, 0, 0
+ * computed in double from the f32 corners (a, b, c) of the node's triangles t in position order,
+ * every sum sequential and every entry rounded to f32 once:
+ *     A_t = 0.5 ((b - a) x (c - a)),  |A_t| = sqrt((A.x A.x + A.y A.y) + A.z A.z),
+ *     x_t = ((a + b) + c) / 3.0
+ *     c  = (sum |A_t| x_t) / (sum |A_t|), or (sum x_t) / count if the area sum is not > 0
+ *     N  = sum A_t
+ *     M  = sum A_t (x_t - c)^T  about the f32-rounded c;  Sxx = M00, Syy = M11, Szz = M22,
+ *          Sxy = 0.5 (M01 + M10), Sxz = 0.5 (M02 + M20), Syz = 0.5 (M12 + M21)
+ *     R2 = max over the corners v of the node's triangles of ((e.x e.x + e.y e.y) + e.z e.z),
+ *          e = v - c (the rounded c), rounded up to f32.
+ * (c is rounded before S and R2 are formed, so that they describe the centre the query uses.)
+ *
+ * The sum, all f64, one rounding per operation, no contraction; f32 values are promoted exactly;
+ * dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z and len(u) = (double)sqrtf((float)dot(u, u)), the f32
+ * square root correctly rounded.
+ *  1. A triangle (A, B, C) seen from p, a = A - p, b = B - p, c = C - p:
+ *       det = (a.x (b.y c.z - b.z c.y) + a.y (b.z c.x - b.x c.z)) + a.z (b.x c.y - b.y c.x)
+ *       la = len(a), lb = len(b), lc = len(c)
+ *       den = (((la lb) lc + dot(a, b) lc) + dot(b, c) la) + dot(c, a) lb
+ *       Omega = 2 h(det, den)
+ *  2. h(num, den), an atan2 from basic operations: with an = |num|, ad = |den|,
+ *       t = (an < ad ? an : ad) / (an < ad ? ad : an)
+ *       h = 0 if num == 0 or t is not finite (a NaN included): a point in the triangle's plane, or at
+ *       a corner, contributes 0.  Otherwise
+ *       u = t > 0.41421356237309503 ? (t - 1) / (t + 1) : t,  base = 0.7853981633974483 or 0,
+ *       z = u u,  P = the Horner form of sum_{k = 0..11} (-1)^k z^k / (2k + 1) from k = 11 down
+ *       (p = p z + c_k, two roundings a step, c_k the double nearest (-1)^k / (2k + 1)),
+ *       h = base + u P;  then, in this order: an > ad: h = 1.5707963267948966 - h;  den < 0:
+ *       h = 3.141592653589793 - h;  num < 0: h = -h.  (Within 1e-11 of atan2.)
+ *  3. A node's expansion, from its moments: r = c - p, d2 = dot(r, r), d = (double)sqrtf((float)d2),
+ *       d3 = d2 d,  s = ((Sxx r.x + Sxy r.y) + Sxz r.z, (Sxy r.x + Syy r.y) + Syz r.z,
+ *       (Sxz r.x + Syz r.y) + Szz r.z),  q = dot(r, s),  tr = (Sxx + Syy) + Szz
+ *       E = dot(N, r) / d3 + (tr / d3 - (3.0 q) / (d3 d2))
+ *     The node is far for p iff d2 > ((double)beta (double)beta) (double)R2.
+ *  4. W = 0; visit(root), where visit(node): far: W += E; else a leaf: W += Omega of its triangles
+ *     in position order; else visit(left), visit(right).  w = (float)(W 0.07957747154594767).
+ *     With NR_TRIMESH_BRUTE W is the sum of Omega over all positions in order; a walk in which no
+ *     node is far gives the same bits.  A point's result does not depend on the other points.
+ *  5. A point with a non-finite coordinate, or a mesh with no live triangle, gives the quiet NaN.
+ *
+ *  - nr_mesh_winding: winding [n] and sdf [n], at least one not NULL; beta finite and >= 0, 0 = 2.0
+ *    (larger: fewer nodes far, closer to the exact sum, slower); flags 0 or NR_TRIMESH_BRUTE; loc for
+ *    X and both outputs.  With sdf the call first runs nr_trimesh_distance's launch for the magnitude
+ *    (the same bits, flags applied to it too) and then writes sdf = w >= 0.5f ? -|sdf| : |sdf|, a NaN
+ *    left as it is: two launches on the stream, nothing read back between them.  With loc = NR_DEVICE
+ *    and no stats the call only enqueues.  Points are taken 64 at a time in the order given and the
+ *    64 share one walk, the union of their cuts through the tree: neighbours in space should be
+ *    neighbours in X (the call does not sort).  stats: ray_steps = n, shade_evals = solid angles and
+ *    expansions evaluated, summed over the points (plus the distance launch's evaluations with sdf),
+ *    launches, ms_total.
+ * Errors of nr_mesh_winding: as nr_trimesh_distance, and NR_E_INVALID for a beta that is negative
+ * or not finite, or winding and sdf both NULL; of nr_mesh_hierarchy: as nr_trimesh_create (with any
+ * NULL argument NR_E_INVALID). */
 typedef struct nr_trimesh nr_trimesh;
 #define NR_TRIMESH_BRUTE 1   /* visit every triangle, no hierarchy: the cross-check and the baseline */
 int nr_obj_load(const char *path, float **vertices /*[nv][3]*/, long *nv, int32_t **triangles /*[nt][3]*/, long *nt);
@@ -771,6 +845,13 @@ int nr_trimesh_info(const nr_trimesh *m, long *nv, long *nt, long *nodes, int *d
 int nr_trimesh_distance(nr_trimesh *m, const float *X /*[n][3]*/, long n, float *sdf /*[n]*/,
                         float *closest /*[n][3]*/, int32_t *tri /*[n]*/, int32_t *feature /*[n]*/, int flags,
                         int loc, nr_stats *stats);
+int nr_mesh_hierarchy(const float *vertices /*[nv][3]*/, long nv, const int32_t *triangles /*[nt][3]*/, long nt,
+                      int leaf /*0 = 8, else 1..32*/, float **nodes /*[nnodes][8]*/, long *nnodes,
+                      int32_t **order /*[ntl]: original index per position*/, long *ntl,
+                      float **moments /*[nnodes][16]*/, int *depth);
+int nr_mesh_winding(nr_trimesh *m, const float *X /*[n][3]*/, long n, float beta /*0 = 2.0*/,
+                    float *winding /*[n] or NULL*/, float *sdf /*[n] or NULL*/,
+                    int flags /*0 or NR_TRIMESH_BRUTE*/, int loc, nr_stats *stats);
 
 /* ---- composed scenes: several networks, placed and combined by CSG ---------------- */
 /* (new symbols and new structs only: NR_ABI_VERSION stays 3, nr_stats is unchanged)

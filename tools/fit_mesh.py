@@ -5,7 +5,11 @@ The mesh: an OBJ file (nr.load_obj), or with no argument the mesh nr_extract_mes
 network's place: --points / 2 points uniform in the ball of radius 1.2 about the mesh (its bound scaled
 into the unit ball), as many on the surface -- the closest points nr_trimesh_distance returns for ball
 points -- jittered by 0.03; the query runs on a Morton-sorted copy (neighbours in space share a walk) and
-the pairs are shuffled afterwards for the fit.  Y = the signed distance, clamp 0.1; a [3, 32 x 4, 1]
+the pairs are shuffled afterwards for the fit.  Y = the signed distance, clamp 0.1 -- its sign the
+pseudonormal's (--sign normal: nr_trimesh_distance) or the winding number's (--sign winding:
+nr_mesh_winding with the sdf output), by default the first for a closed mesh and the second for any
+other; --drop-x LO HI removes the triangles whose centroid has LO <= x <= HI first, to make an open mesh
+of a closed one.  A [3, 32 x 4, 1]
 student, batch 2^16, lr 1e-3, --epochs epochs; then load_into a renderer and a 256^2 frame, whose
 silhouette is compared with the source network's when the mesh came from one.
 Runs on the GPU box: python3 tools/fit_mesh.py [mesh.obj]"""
@@ -30,6 +34,8 @@ def main():
     ap.add_argument("--points", type=int, default=1 << 21)
     ap.add_argument("--epochs", type=int, default=400)
     ap.add_argument("--out", help="write the student's frame here (.png)")
+    ap.add_argument("--sign", choices=("normal", "winding"), help="default: normal for a closed mesh, winding otherwise")
+    ap.add_argument("--drop-x", type=float, nargs=2, metavar=("LO", "HI"), help="remove the triangles whose centroid has LO <= x <= HI")
     args = ap.parse_args()
     n = args.points
     dev = torch.device("cuda:0")
@@ -52,13 +58,21 @@ def main():
         mesh = source.extract_mesh((-1.0, -1.0, -1.0), (step, step, step), (args.size,) * 3, normals=False)
         V, T = mesh["vertices"], mesh["triangles"]
         print(f"plane_1 through nr_extract_mesh at {args.size}^3: {len(V)} vertices, {len(T)} triangles")
+    if args.drop_x:
+        cx = V[T].astype(np.float64).mean(1)[:, 0]
+        keep = (cx < args.drop_x[0]) | (cx > args.drop_x[1])
+        print(f"--drop-x: {int((~keep).sum())} of {len(T)} triangles with {args.drop_x[0]} <= x <= {args.drop_x[1]} removed")
+        T = np.ascontiguousarray(T[keep])
     owner = nr.Renderer(0)
     owner.set_stream(stream.cuda_stream)
     with nr.TriMesh(owner, V, T) as m:
         info = m.info()
         print(f"TriMesh: {info['nodes']} nodes, depth {info['depth']}, closed {info['closed']}")
-        if not info["closed"]:
-            print("the mesh is not closed: the sign of the distance means nothing, and so does the fit")
+        sign = args.sign or ("normal" if info["closed"] else "winding")
+        if not info["closed"] and not args.sign:
+            print("the mesh is not closed: the sign is taken from the winding number (w >= 0.5 is inside), as with --sign winding")
+        elif not info["closed"] and sign == "normal":
+            print("the mesh is not closed: the pseudonormal sign of the distance means nothing, and so does the fit")
         d = torch.randn((n // 2, 3), generator=gen, device=dev)
         u = torch.rand((n // 2, 1), generator=gen, device=dev)
         ball = (d / d.norm(dim=1, keepdim=True) * 1.2 * u.pow(1.0 / 3.0)).float()
@@ -71,9 +85,12 @@ def main():
         X = X[morton_order(X, -1.3, 1.3)].float().contiguous()
         Y = torch.zeros(n, dtype=torch.float32, device=dev)
         torch.cuda.synchronize()
-        st1 = m.distance_device(X.data_ptr(), n, Y.data_ptr(), with_stats=True)
+        if sign == "winding":
+            st1 = m.winding_device(X.data_ptr(), n, sdf_ptr=Y.data_ptr(), with_stats=True)
+        else:
+            st1 = m.distance_device(X.data_ptr(), n, Y.data_ptr(), with_stats=True)
     print(f"samples: {n // 2} ball points -> closest points in {st0['ms_total']:.2f} ms ({st0['shade_evals'] / (n // 2):.1f} "
-          f"evaluations per point); {n} signed distances in {st1['ms_total']:.2f} ms ({st1['shade_evals'] / n:.1f} per point); "
+          f"evaluations per point); {n} signed distances (sign: {sign}) in {st1['ms_total']:.2f} ms ({st1['shade_evals'] / n:.1f} per point); "
           f"{float((Y < 0).float().mean()):.4f} of them inside, |Y| < clamp at {float((Y.abs() < CLAMP).float().mean()):.3f}")
     perm = torch.randperm(n, generator=gen, device=dev)
     X, Y = X[perm].contiguous(), Y[perm].contiguous()
