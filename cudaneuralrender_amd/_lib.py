@@ -52,9 +52,12 @@ EXPORTS = [
     "nr_fit_create", "nr_fit_destroy", "nr_fit_num_params", "nr_fit_gradient", "nr_fit_run", "nr_fit_weights",
     "nr_obj_load", "nr_trimesh_normals", "nr_trimesh_create", "nr_trimesh_destroy", "nr_trimesh_info",
     "nr_trimesh_distance", "nr_mesh_hierarchy", "nr_mesh_winding",
+    "nr_mesh_trace_rays", "nr_mesh_gbuffer", "nr_mesh_render",
 ]
 # nr_trimesh_distance: flags, and the feature codes of its `feature` output
 NR_TRIMESH_BRUTE = 1
+# nr_mesh_trace_rays / nr_mesh_gbuffer / nr_mesh_render: further flags
+NR_MESH_RAY_ANY, NR_MESH_RAY_SMOOTH = 2, 4
 NR_TRIMESH_FEATURE = ("face", "edge AB", "edge BC", "edge CA", "vertex A", "vertex B", "vertex C")
 # composed scenes (nr_compose_*): limits and part ops
 NR_COMPOSE_MAX_NETS, NR_COMPOSE_MAX_PARTS = 4, 16
@@ -304,6 +307,10 @@ def lib():
         "nr_mesh_hierarchy": (I, [P, L64, P, L64, I, ctypes.POINTER(FP), ctypes.POINTER(L64), ctypes.POINTER(IP),
                                   ctypes.POINTER(L64), ctypes.POINTER(FP), IP]),
         "nr_mesh_winding": (I, [P, P, L64, ctypes.c_float, P, P, I, I, ctypes.POINTER(NRStats)]),
+        "nr_mesh_trace_rays": (I, [P, P, P, L64, ctypes.c_float, ctypes.c_float, P, P, P, P, P, P, I, I,
+                                   ctypes.POINTER(NRStats)]),
+        "nr_mesh_gbuffer": (I, [P, I, I, P, P, P, P, P, P, I, I, ctypes.POINTER(NRStats)]),
+        "nr_mesh_render": (I, [P, P, I, I, I, I, ctypes.POINTER(NRStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -8,15 +8,16 @@
 
 using namespace nr;
 
-// ---- triangle meshes (nr_trimesh_*; nr_trimesh_host.cpp, nr_trimesh.hip, nr_winding.hip) ----
+// ---- triangle meshes (nr_trimesh_*; nr_trimesh_host.cpp, nr_trimesh.hip, nr_winding.hip, nr_mesh_rays.hip) ----
 // The hierarchy with its moments, the reordered triangles and the pseudonormal table are built on
 // the host at create time and live on the device; a distance query is one launch, a winding query
-// one, or two with the sdf output.
+// one, or two with the sdf output, a ray query (nr_mesh_rays.hip) one.
 struct nr_trimesh {
     nr_ctx *owner = nullptr;
     long nv = 0, nt = 0, nnodes = 0, ntl = 0;
     int depth = 0, closed = 0;
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    float scale = 0;              // largest |coordinate| + largest axis extent: the boxes' slack times 2^18
     float *d_nodes = nullptr, *d_tris = nullptr, *d_table = nullptr, *d_moments = nullptr;
     unsigned long long *d_stats = nullptr;
     float *d_io = nullptr;        // staging of host points and results
@@ -49,6 +50,7 @@ int nr_trimesh_create(nr_ctx *owner, const float *vertices, long nv, const int32
     }
     m->nnodes = H.nnodes; m->ntl = H.ntl; m->depth = H.depth;
     for (int a = 0; a < 3; ++a) { m->lo[a] = H.lo[a]; m->hi[a] = H.hi[a]; }
+    m->scale = std::ldexp(H.slack, TRIMESH_SLACK_SHIFT);
     hipError_t e = hipSetDevice(owner->device);
     hipStream_t s = e == hipSuccess ? cur_stream(owner) : nullptr;
     if (e == hipSuccess && owner->use_own && !owner->own_stream) { delete m; return NR_E_HIP; }
@@ -192,6 +194,105 @@ int nr_mesh_winding(nr_trimesh *m, const float *X, long n, float beta, float *wi
     st.launches = A.sdf ? 3 : 2;  // the counter's memset, k_trimesh_distance for sdf, k_trimesh_winding
     *stats = st;
     return NR_OK;
+}
+
+}  // extern "C"
+
+// n caller-supplied rays, or with origins == NULL the W x H pixel rays of the owner's view, through
+// one k_mesh_rays launch; with `out` the payload is the frame (nr_mesh_render).
+static int mesh_rays(nr_trimesh *m, const char *fn, const float *origins, const float *dirs, long n, int W, int H, float tmin,
+                     float tmax, int32_t *status, float *t, int32_t *tri, float *bary, float *position, float *normal,
+                     uint32_t *out, int flags, int loc, nr_stats *stats) {
+    nr_ctx *c = m->owner;
+    if (flags & ~(NR_TRIMESH_BRUTE | NR_MESH_RAY_ANY | NR_MESH_RAY_SMOOTH)) return set_err(c, NR_E_INVALID, "%s: unknown flag bits %#x", fn, flags);
+    if (flags & NR_MESH_RAY_ANY) {
+        if (flags & NR_MESH_RAY_SMOOTH) return set_err(c, NR_E_INVALID, "%s: NR_MESH_RAY_ANY with NR_MESH_RAY_SMOOTH", fn);
+        if (t || tri || bary || position || normal || out) return set_err(c, NR_E_INVALID, "%s: NR_MESH_RAY_ANY gives status only", fn);
+    }
+    if (out && c->color_type == NR_COLOR_MATCAP && !c->d_matcap) return set_err(c, NR_E_STATE, "%s: matcap colouring without a matcap", fn);
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const size_t N = (size_t)n;
+    MeshRayArgs R{};
+    R.origins = origins; R.dirs = dirs; R.n = n;
+    R.W = W; R.H = H; R.tiles_x = (W + 7) / 8; R.tiles_y = (H + 7) / 8;
+    R.rcp_w = pow2_rcp(W); R.rcp_h = pow2_rcp(H);
+    memcpy(R.inv_view, c->inv_view, sizeof R.inv_view);
+    R.nodes = m->d_nodes; R.tris = m->d_tris; R.table = m->d_table;
+    R.nnodes = (int)m->nnodes; R.ntl = (int)m->ntl;
+    R.brute = (flags & NR_TRIMESH_BRUTE) != 0;
+    R.any = (flags & NR_MESH_RAY_ANY) != 0;
+    R.smooth = (flags & NR_MESH_RAY_SMOOTH) != 0;
+    R.tmin = tmin; R.tmax = tmax;
+    R.scale = m->scale;
+    R.status = status; R.t = t; R.tri = tri; R.bary = bary; R.position = position; R.normal = normal;
+    R.stats = m->d_stats;
+    RenderArgs A{};
+    if (out) {
+        A = render_args(c, W, H, H, H, 1, 0, 0);
+        A.out = out;
+        A.frame = c->frame;
+        memcpy(A.inv_view, c->inv_view, sizeof A.inv_view);
+        memcpy(A.normal, c->normal, sizeof A.normal);
+    }
+    // staged: the rays, then every output the caller asked for
+    Staging io(loc);
+    io.in(R.origins, 3 * N); io.in(R.dirs, 3 * N);
+    io.out(R.status, N); io.out(R.t, N); io.out(R.tri, N); io.out(R.bary, 3 * N); io.out(R.position, 3 * N);
+    io.out(R.normal, 3 * N); io.out(A.out, N);
+    int rc;
+    if ((rc = io.begin(c, m->d_io, m->cap_io, s)) != NR_OK) return rc;
+    // a grid-stride over chunks of 64 rays: at most 8 four-wave workgroups per CU
+    const size_t chunks = origins ? (N + 63) / 64 : (size_t)R.tiles_x * (size_t)R.tiles_y;
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((chunks + 3) / 4, (size_t)num_cus(c->device) * 8));
+    nr_stats st{};
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, hipMemsetAsync(m->d_stats, 0, 16, s));
+    HIPCHK(c, launch_mesh_rays(R, out ? &A : nullptr, grid, s));
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if ((rc = io.end(c, s)) != NR_OK) return rc;
+    unsigned long long counts[2] = {0, 0};
+    if (stats) HIPCHK(c, hipMemcpyAsync(counts, m->d_stats, 16, hipMemcpyDeviceToHost, s));
+    rc = end_timed(c, stats != nullptr, loc, s, &st.ms_total);
+    if (rc != NR_OK || !stats) return rc;
+    st.ray_steps = (uint64_t)n;
+    st.shade_evals = counts[0];
+    st.rays_hit = counts[1];
+    st.launches = 2;  // the counters' memset and k_mesh_rays
+    *stats = st;
+    return NR_OK;
+}
+
+extern "C" {
+
+int nr_mesh_trace_rays(nr_trimesh *m, const float *origins, const float *dirs, long n, float tmin, float tmax, int32_t *status,
+                       float *t, int32_t *tri, float *bary, float *position, float *normal, int flags, int loc,
+                       nr_stats *stats) {
+    if (!m) return set_err(nullptr, NR_E_INVALID, "nr_mesh_trace_rays: mesh is NULL");
+    nr_ctx *c = m->owner;
+    if (!origins || !dirs) return set_err(c, NR_E_INVALID, "nr_mesh_trace_rays: NULL rays");
+    if (n < 1 || n > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_mesh_trace_rays: n = %ld outside [1, 2^30]", n);
+    if (!(tmin <= tmax)) return set_err(c, NR_E_INVALID, "nr_mesh_trace_rays: tmin = %g, tmax = %g: a NaN, or tmin > tmax", (double)tmin, (double)tmax);
+    return mesh_rays(m, "nr_mesh_trace_rays", origins, dirs, n, 1, 1, tmin, tmax, status, t, tri, bary, position, normal, nullptr,
+                     flags, loc, stats);
+}
+
+int nr_mesh_gbuffer(nr_trimesh *m, int W, int H, int32_t *status, float *t, int32_t *tri, float *bary, float *position,
+                    float *normal, int flags, int loc, nr_stats *stats) {
+    if (!m) return set_err(nullptr, NR_E_INVALID, "nr_mesh_gbuffer: mesh is NULL");
+    nr_ctx *c = m->owner;
+    if (W < 1 || H < 1 || (long)W * H > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_mesh_gbuffer: bad size %dx%d", W, H);
+    return mesh_rays(m, "nr_mesh_gbuffer", nullptr, nullptr, (long)W * H, W, H, 0.0f, INFINITY, status, t, tri, bary, position,
+                     normal, nullptr, flags, loc, stats);
+}
+
+int nr_mesh_render(nr_trimesh *m, uint32_t *out, int W, int H, int flags, int out_loc, nr_stats *stats) {
+    if (!m) return set_err(nullptr, NR_E_INVALID, "nr_mesh_render: mesh is NULL");
+    nr_ctx *c = m->owner;
+    if (!out) return set_err(c, NR_E_INVALID, "nr_mesh_render: out is NULL");
+    if (W < 1 || H < 1 || (long)W * H > (1l << 30)) return set_err(c, NR_E_INVALID, "nr_mesh_render: bad size %dx%d", W, H);
+    return mesh_rays(m, "nr_mesh_render", nullptr, nullptr, (long)W * H, W, H, 0.0f, INFINITY, nullptr, nullptr, nullptr, nullptr,
+                     nullptr, nullptr, out, flags, out_loc, stats);
 }
 
 }  // extern "C"

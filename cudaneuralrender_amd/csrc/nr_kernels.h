@@ -335,6 +335,29 @@ struct TriWindArgs {
 };
 hipError_t launch_trimesh_winding(const TriWindArgs &A, int grid, hipStream_t st);  // 4-wave workgroups
 
+// Rays against a triangle mesh (nr_mesh_rays.hip k_mesh_rays; nr_mesh_trace_rays, nr_mesh_gbuffer,
+// nr_mesh_render): every ray writes its slot of the outputs that are not NULL.  A chunk of 64 rays
+// is 64 consecutive caller rays, or with origins == NULL one 8 x 8 tile of the W x H view.
+struct MeshRayArgs {
+    const float *origins, *dirs;  // [n][3]; both NULL: the pixel rays of the W x H view below
+    long n;                       // 1 .. 2^30 (W H for pixel rays)
+    int W, H, tiles_x, tiles_y;   // pixel rays: the view and its 8 x 8 tiles
+    float rcp_w, rcp_h;           // pow2_rcp(W), pow2_rcp(H) (pixel_uv)
+    float inv_view[12];
+    const float *nodes, *tris;    // [nnodes][8], [ntl][12]
+    const float *table;           // [nt][7][3] pseudonormals, original triangle order
+    int nnodes, ntl;
+    int brute, any, smooth;       // NR_TRIMESH_BRUTE, NR_MESH_RAY_ANY, NR_MESH_RAY_SMOOTH
+    float tmin, tmax;
+    float scale;                  // S of the per-ray pad: 2^18 times the slack of the boxes
+    int32_t *status, *tri;        // [n]
+    float *t, *bary, *position, *normal;  // [n], [n][3] x 3
+    unsigned long long *stats;    // [0] ray-triangle evaluations, [1] hits (zeroed before the launch)
+};
+// 4-wave workgroups; with `color` the frame A.out of shade_color (A: render_args, the view and the
+// normal matrix) instead of the hit record
+hipError_t launch_mesh_rays(const MeshRayArgs &R, const RenderArgs *color, int grid, hipStream_t st);
+
 // Composed scenes (nr_compose.hip; nr_compose_*): the distinct fp32 packs back to back in one device
 // buffer (staged into dynamic LDS in that order), the parts, and the queried rays or points.  The
 // struct travels in the kernarg segment: the part loop is wave-uniform and reads it with scalar loads.

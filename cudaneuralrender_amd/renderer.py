@@ -13,7 +13,7 @@ from ._lib import (NR_AA_CONTRAST_DEFAULT, NR_AA_MODE, NR_COLOR_FACING, NR_COLOR
                    NR_GROUP_COPY, NR_HOST, NR_PRECISION, NR_SCENE, NR_SCHEDULE, NRFrame, NRKernelProf, NRLight, NRProjectOpts,
                    NRStats, check, lib)
 from ._lib import NR_PART_OP, NRComposeStats, NRFitOpts, NRPart
-from ._lib import NR_TRIMESH_BRUTE
+from ._lib import NR_MESH_RAY_ANY, NR_MESH_RAY_SMOOTH, NR_TRIMESH_BRUTE
 
 _FP = ctypes.POINTER(ctypes.c_float)
 
@@ -1460,4 +1460,96 @@ class TriMesh:
         self._chk(self._L.nr_mesh_winding(self._m, vp[0], int(n), float(beta), vp[1], vp[2],
                                           NR_TRIMESH_BRUTE if brute else 0, NR_DEVICE,
                                           ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
+    # -- rays (nr_mesh_trace_rays, nr_mesh_gbuffer, nr_mesh_render)
+    _RAY_KEYS = ("status", "t", "tri", "bary", "position", "normal")
+
+    @staticmethod
+    def _ray_flags(smooth, any_hit, brute):
+        return (NR_MESH_RAY_SMOOTH if smooth else 0) | (NR_MESH_RAY_ANY if any_hit else 0) | (NR_TRIMESH_BRUTE if brute else 0)
+
+    @staticmethod
+    def _ray_outputs(shape, tri, bary, position, normal, any_hit):
+        out = {"status": np.zeros(shape, np.int32)}
+        if not any_hit:
+            out["t"] = np.zeros(shape, np.float32)
+            if tri:
+                out["tri"] = np.zeros(shape, np.int32)
+            for key, want in (("bary", bary), ("position", position), ("normal", normal)):
+                if want:
+                    out[key] = np.zeros(shape + (3,), np.float32)
+        return out
+
+    def trace_rays(self, origins, dirs, tmin=0.0, tmax=float("inf"), tri=True, bary=False, position=True, normal=True,
+                   smooth=False, any_hit=False, brute=False, with_stats=False):
+        """nr_mesh_trace_rays on host arrays: the closest hit of each ray p = origins[i] + t * dirs[i]
+        (dirs as given) with tmin <= t <= tmax, bit for bit the arithmetic of include/neural_render.h.
+        Returns {"status" (NR_RAY_HIT / NR_RAY_MISS), "t"[, "tri", "bary" [n, 3], "position" [n, 3],
+        "normal" [n, 3]]}; smooth: the normal interpolated from the vertex pseudonormals instead of
+        the face's.  any_hit: {"status"} only -- is anything hit (shadow and occlusion rays).  brute:
+        every triangle, no hierarchy (the same bits).  Neighbours in space should be neighbours in
+        the arrays."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError(f"origins {o.shape} and dirs {d.shape} differ")
+        n = o.shape[0]
+        out = self._ray_outputs((n,), tri, bary, position, normal, any_hit)
+        ptr = [out[k].ctypes.data if k in out else None for k in self._RAY_KEYS]
+        st = NRStats()
+        self._chk(self._L.nr_mesh_trace_rays(self._m, o.ctypes.data, d.ctypes.data, n, float(tmin), float(tmax), *ptr,
+                                             self._ray_flags(smooth, any_hit, brute), NR_HOST,
+                                             ctypes.byref(st) if with_stats else None))
+        return (out, st.as_dict()) if with_stats else out
+
+    def trace_rays_device(self, origins_ptr, dirs_ptr, n, tmin=0.0, tmax=float("inf"), status_ptr=None, t_ptr=None,
+                          tri_ptr=None, bary_ptr=None, position_ptr=None, normal_ptr=None, smooth=False, any_hit=False,
+                          brute=False, with_stats=False):
+        """nr_mesh_trace_rays on device buffers (float32 [n, 3] rays, int32 status / tri, float32 t,
+        [n, 3] bary / position / normal); None = that output is not wanted.  Runs on the renderer's
+        stream and, without stats, returns without waiting."""
+        vp = [ctypes.c_void_p(p) if p else None
+              for p in (origins_ptr, dirs_ptr, status_ptr, t_ptr, tri_ptr, bary_ptr, position_ptr, normal_ptr)]
+        st = NRStats()
+        self._chk(self._L.nr_mesh_trace_rays(self._m, vp[0], vp[1], int(n), float(tmin), float(tmax), *vp[2:],
+                                             self._ray_flags(smooth, any_hit, brute), NR_DEVICE,
+                                             ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
+    def gbuffer(self, W, H, tri=True, bary=False, position=True, normal=True, smooth=False, any_hit=False, brute=False,
+                with_stats=False):
+        """nr_mesh_gbuffer: the trace_rays outputs for the W x H pixel rays of the renderer's view
+        (Renderer.render's rays), shaped (H, W) and (H, W, 3)."""
+        out = self._ray_outputs((H, W), tri, bary, position, normal, any_hit)
+        ptr = [out[k].ctypes.data if k in out else None for k in self._RAY_KEYS]
+        st = NRStats()
+        self._chk(self._L.nr_mesh_gbuffer(self._m, int(W), int(H), *ptr, self._ray_flags(smooth, any_hit, brute), NR_HOST,
+                                          ctypes.byref(st) if with_stats else None))
+        return (out, st.as_dict()) if with_stats else out
+
+    def gbuffer_device(self, W, H, status_ptr=None, t_ptr=None, tri_ptr=None, bary_ptr=None, position_ptr=None,
+                       normal_ptr=None, smooth=False, any_hit=False, brute=False, with_stats=False):
+        """nr_mesh_gbuffer into device buffers; None = that output is not wanted."""
+        vp = [ctypes.c_void_p(p) if p else None for p in (status_ptr, t_ptr, tri_ptr, bary_ptr, position_ptr, normal_ptr)]
+        st = NRStats()
+        self._chk(self._L.nr_mesh_gbuffer(self._m, int(W), int(H), *vp, self._ray_flags(smooth, any_hit, brute), NR_DEVICE,
+                                          ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
+    def render(self, W, H, smooth=False, brute=False, with_stats=True):
+        """nr_mesh_render: the mesh through the renderer's view, coloured as Renderer.render colours
+        its normals (set_color_type / set_matcap of the renderer); (img [H, W] uint32, stats)."""
+        out = np.zeros((H, W), np.uint32)
+        st = NRStats()
+        self._chk(self._L.nr_mesh_render(self._m, out.ctypes.data, int(W), int(H), self._ray_flags(smooth, False, brute),
+                                         NR_HOST, ctypes.byref(st) if with_stats else None))
+        return (out, st.as_dict()) if with_stats else out
+
+    def render_device(self, out_ptr, W, H, smooth=False, brute=False, with_stats=False):
+        """nr_mesh_render into a device buffer (uint32 [H, W])."""
+        st = NRStats()
+        self._chk(self._L.nr_mesh_render(self._m, ctypes.c_void_p(out_ptr), int(W), int(H),
+                                         self._ray_flags(smooth, False, brute), NR_DEVICE,
+                                         ctypes.byref(st) if with_stats else None))
         return st.as_dict() if with_stats else None

@@ -853,6 +853,92 @@ int nr_mesh_winding(nr_trimesh *m, const float *X /*[n][3]*/, long n, float beta
                     float *winding /*[n] or NULL*/, float *sdf /*[n] or NULL*/,
                     int flags /*0 or NR_TRIMESH_BRUTE*/, int loc, nr_stats *stats);
 
+/* ---- triangle meshes: ray casting and geometry buffers -------------------------------- */
+/* (new symbols only: NR_ABI_VERSION stays 3, nr_stats is unchanged)
+ * The third query of a nr_trimesh: rays.  nr_mesh_trace_rays casts caller-supplied rays,
+ * nr_mesh_gbuffer the W x H pixel rays of the owner's view (nr_render's rays), nr_mesh_render shades
+ * those into a frame.  The result is the closest hit of each ray, or with NR_MESH_RAY_ANY whether
+ * there is any hit (occlusion and shadow rays).
+ *
+ * The contract, all f32, one rounding per operation, no contraction except the fmaf named; every `/`
+ * one correctly rounded division; a comparison with a NaN is false.  The ray-triangle test is the
+ * shear form of Woop, Benthin and Wald (Watertight Ray/Triangle Intersection, JCGT 2013): the edge
+ * function of an edge shared by two triangles is the exact negation of the neighbour's, so no ray
+ * slips between two triangles of a closed mesh.
+ *  1. Per ray (o, d).  The ray is dead if any of its six numbers is not finite or d = (0, 0, 0): it
+ *     returns MISS.  Otherwise kz = 0; if |d.y| > |d[kz]| then kz = 1; if |d.z| > |d[kz]| then kz = 2;
+ *     kx = (kz + 1) % 3, ky = (kx + 1) % 3, swapped if d[kz] < 0;
+ *       Sx = d[kx] / d[kz],  Sy = d[ky] / d[kz],  Sz = 1.0f / d[kz].
+ *  2. Per live triangle (a, b, c) -- one whose face entry in the pseudonormal table is not (0, 0, 0);
+ *     a zero-area triangle is never hit, by definition:
+ *       A = a - o, B = b - o, C = c - o (componentwise)
+ *       Px = P[kx] - Sx * P[kz],  Py = P[ky] - Sy * P[kz]           for P in A, B, C
+ *       U = Cx * By - Cy * Bx,  V = Ax * Cy - Ay * Cx,  W = Bx * Ay - By * Ax
+ *     (two products and one subtraction each).  The triangle is missed if
+ *       (U < 0 || V < 0 || W < 0) && (U > 0 || V > 0 || W > 0)
+ *     -- no back-face culling, no f64 fallback.  det = (U + V) + W; missed unless det != 0.  Then
+ *       Pz = Sz * P[kz] for P in A, B, C;  Tn = (U * Az + V * Bz) + W * Cz;  t = Tn / det
+ *     and the triangle is hit iff tmin <= t && t <= tmax.
+ *  3. Closest hit: the winner is the lexicographic minimum of (t, original triangle index) over all
+ *     hit triangles.  A minimum does not depend on the order it is taken in: the result is the same
+ *     bits for any traversal, leaf size, grid, or with NR_TRIMESH_BRUTE.  A ray with a winner has
+ *       status   = NR_RAY_HIT (2)
+ *       t, tri   = the winner's t and its index in the caller's triangles
+ *       bary     = (U / det, V / det, W / det): the weights of a, b, c
+ *       position = fmaf(d, t, o), componentwise
+ *       normal   = the table's face entry N[tri][0] as stored, not turned towards the ray; or with
+ *                  NR_MESH_RAY_SMOOTH, with normalise(v) = v * (1.0f / sqrtf((v.x v.x + v.y v.y) +
+ *                  v.z v.z)) (nr_trace_rays' normal): n_k = normalise(N[tri][4 + k]) for the corners
+ *                  k = A, B, C, the face entry instead where the corner's squared length is 0 or not
+ *                  finite; m = fmaf(n_C, bary[2], fmaf(n_B, bary[1], n_A * bary[0])) componentwise;
+ *                  normal = normalise(m), the face entry where m's squared length is 0 or not finite.
+ *     Every other ray, a dead one included, has status = NR_RAY_MISS (0), tri = -1 and t, bary,
+ *     position, normal all +0.0.
+ *  4. NR_MESH_RAY_ANY: status = NR_RAY_HIT iff some live triangle is hit under step 2, else
+ *     NR_RAY_MISS; existence does not depend on the traversal.  Only status may be asked for.
+ *  5. The walk (not part of the bits, only of the cost).  A node is left out only if no ray that
+ *     shares the walk wants it.  A ray wants a node unless tn > tf, or tf < tmin, or tn > min(best,
+ *     tmax) (strict: a tie in t with a smaller index is still found), where best is the ray's
+ *     smallest t so far and [tn, tf] its slab interval of the node's stored (grown) box widened by
+ *       pad = 2^-18 * (max(|o.x|, |o.y|, |o.z|) + S),
+ *     S = the scale of the boxes' slack (largest |coordinate| + largest axis extent of the vertices):
+ *       t1, t2 = ((lo - pad) - o) * (1.0f / d), ((hi + pad) - o) * (1.0f / d)     per axis
+ *       tn = max over the axes of min(t1, t2),  tf = min over the axes of max(t1, t2)
+ *     with min and max that ignore a NaN.  The rounding of step 2 scales with |a - o|, not with the
+ *     mesh, which is why the pad depends on the origin.  The result is therefore that of step 3
+ *     whenever every hit's t lies inside the slab interval of its triangle's widened box -- always
+ *     in tests/test_mesh_rays_cpu.py, origins up to |o| = 100 included; with NR_TRIMESH_BRUTE
+ *     unconditionally.
+ *
+ *  - nr_mesh_trace_rays: dirs is used as given and t is in units of d; tmin <= tmax, neither a NaN,
+ *    tmax may be +INFINITY.  Any of status [n], t [n], tri [n], bary [n][3], position [n][3],
+ *    normal [n][3] may be NULL; loc = NR_HOST or NR_DEVICE for the rays and all of them.  One launch;
+ *    with loc = NR_DEVICE and no stats the call only enqueues.  Rays are taken 64 at a time in the
+ *    order given and the 64 share one walk: rays that are neighbours in space should be neighbours in
+ *    the arrays (the call does not sort).  stats (may be NULL): ray_steps = n, rays_hit = the HITs,
+ *    shade_evals = ray-triangle evaluations summed over the live rays, launches, ms_total;
+ *    everything else 0.
+ *  - nr_mesh_gbuffer: the W x H pixel rays of the owner's view (nr_set_view), generated in the kernel
+ *    with nr_render's arithmetic; pixel (x, y) is at index y * W + x; tmin = 0, tmax = +INFINITY.  A
+ *    wave takes one 8 x 8 pixel tile.  W * H <= 2^30.
+ *  - nr_mesh_render: the same rays; a HIT pixel is nr_render's colour of (normal, ray direction) with
+ *    the owner's colouring (nr_set_static's colour type, nr_set_matcap, the normal matrix of
+ *    nr_set_view), every other pixel 0.  NR_E_STATE for matcap colouring without a matcap, as
+ *    nr_render.  flags: NR_TRIMESH_BRUTE and NR_MESH_RAY_SMOOTH.
+ * Errors: as nr_trimesh_distance (a NULL mesh, n outside [1, 2^30], an unknown flag bit, NR_E_HIP,
+ * NR_E_NOMEM), and NR_E_INVALID for NULL origins or dirs, a tmin or tmax that is a NaN or tmin > tmax,
+ * W or H < 1, W * H > 2^30, a NULL out, NR_MESH_RAY_ANY with NR_MESH_RAY_SMOOTH or with any output
+ * other than status.  A mesh with no live triangle gives MISS everywhere. */
+#define NR_MESH_RAY_ANY    2  /* status only: is any triangle hit in [tmin, tmax] */
+#define NR_MESH_RAY_SMOOTH 4  /* normal interpolated from the vertex pseudonormals */
+int nr_mesh_trace_rays(nr_trimesh *m, const float *origins /*[n][3]*/, const float *dirs /*[n][3]*/, long n,
+                       float tmin, float tmax, int32_t *status /*[n]*/, float *t /*[n]*/, int32_t *tri /*[n]*/,
+                       float *bary /*[n][3]*/, float *position /*[n][3]*/, float *normal /*[n][3]*/, int flags,
+                       int loc, nr_stats *stats);
+int nr_mesh_gbuffer(nr_trimesh *m, int W, int H, int32_t *status, float *t, int32_t *tri, float *bary,
+                    float *position, float *normal, int flags, int loc, nr_stats *stats);
+int nr_mesh_render(nr_trimesh *m, uint32_t *out /*[H][W]*/, int W, int H, int flags, int out_loc, nr_stats *stats);
+
 /* ---- composed scenes: several networks, placed and combined by CSG ---------------- */
 /* (new symbols and new structs only: NR_ABI_VERSION stays 3, nr_stats is unchanged)
  *

@@ -11,7 +11,8 @@ nr_mesh_winding with the sdf output), by default the first for a closed mesh and
 other; --drop-x LO HI removes the triangles whose centroid has LO <= x <= HI first, to make an open mesh
 of a closed one.  A [3, 32 x 4, 1]
 student, batch 2^16, lr 1e-3, --epochs epochs; then load_into a renderer and a 256^2 frame, whose
-silhouette is compared with the source network's when the mesh came from one.
+silhouette is compared with the mesh's own (TriMesh.gbuffer through the same camera) and, when the
+mesh came from a network, with that network's.
 Runs on the GPU box: python3 tools/fit_mesh.py [mesh.obj]"""
 import argparse
 import os
@@ -73,6 +74,13 @@ def main():
             print("the mesh is not closed: the sign is taken from the winding number (w >= 0.5 is inside), as with --sign winding")
         elif not info["closed"] and sign == "normal":
             print("the mesh is not closed: the pseudonormal sign of the distance means nothing, and so does the fit")
+        # the mesh itself through the camera silhouette() renders the networks with
+        iv, nm = nr.camera(0.0, 0.0, 2.0)
+        owner.set_view(iv, nm, 0)
+        gb, gst = m.gbuffer(256, 256, tri=False, position=False, normal=False, with_stats=True)
+        sm = gb["status"] == 2  # NR_RAY_HIT
+        print(f"mesh at 256^2: {int(sm.sum())} px in {gst['ms_total']:.2f} ms ({gst['shade_evals'] / sm.size:.1f} ray-triangle "
+              f"evaluations per pixel)")
         d = torch.randn((n // 2, 3), generator=gen, device=dev)
         u = torch.rand((n // 2, 1), generator=gen, device=dev)
         ball = (d / d.norm(dim=1, keepdim=True) * 1.2 * u.pow(1.0 / 3.0)).float()
@@ -122,13 +130,17 @@ def main():
     if args.out:
         img, _ = student.render(256, 256, 256)
         nr.save_png(args.out, img)
+    iou = lambda a, b: float((a & b).sum() / max((a | b).sum(), 1))
+    # against the mesh: the student's own zero set (scene tanh, as the mesh was rendered), not silhouette()'s scene
+    student.set_scene("tanh")
+    sz = student.render(256, 256, 256)[0] != 0
+    print(f"silhouette at 256^2, scene tanh: mesh {int(sm.sum())} px, student fitted to it {int(sz.sum())} px, IoU against the mesh "
+          f"{iou(sm, sz):.4f}")
     if source is not None:
         st = silhouette(source)
-        print(f"silhouette at 256^2: source network {int(st.sum())} px, student fitted to its mesh {int(ss.sum())} px, "
-              f"IoU {float((st & ss).sum() / max((st | ss).sum(), 1)):.4f}")
+        print(f"silhouette at 256^2, scene v1: source network {int(st.sum())} px, student fitted to its mesh {int(ss.sum())} px, "
+              f"IoU {iou(st, ss):.4f}")
         source.close()
-    else:
-        print(f"silhouette at 256^2: student {int(ss.sum())} px (no source network to compare with)")
     student.close()
     owner.close()
 
