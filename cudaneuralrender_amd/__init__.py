@@ -19,6 +19,8 @@ from ._lib import NRFitOpts  # noqa: F401
 from .renderer import Fit  # noqa: F401
 from ._lib import NR_TRIMESH_BRUTE, NR_TRIMESH_FEATURE  # noqa: F401
 from .renderer import TriMesh, load_obj, trimesh_hierarchy, trimesh_normals  # noqa: F401
+from ._lib import NR_ORDER, NR_SAMPLE_SIGN, NRSampleOpts  # noqa: F401
+from .renderer import mesh_area_table  # noqa: F401
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_DIR = os.path.dirname(PKG_DIR)

@@ -53,11 +53,15 @@ EXPORTS = [
     "nr_obj_load", "nr_trimesh_normals", "nr_trimesh_create", "nr_trimesh_destroy", "nr_trimesh_info",
     "nr_trimesh_distance", "nr_mesh_hierarchy", "nr_mesh_winding",
     "nr_mesh_trace_rays", "nr_mesh_gbuffer", "nr_mesh_render",
+    "nr_mesh_area_table", "nr_mesh_sample", "nr_points_order", "nr_mesh_fit_samples",
 ]
 # nr_trimesh_distance: flags, and the feature codes of its `feature` output
 NR_TRIMESH_BRUTE = 1
 # nr_mesh_trace_rays / nr_mesh_gbuffer / nr_mesh_render: further flags
 NR_MESH_RAY_ANY, NR_MESH_RAY_SMOOTH = 2, 4
+# nr_mesh_fit_samples: where the sign of Y comes from; nr_points_order: the key
+NR_SAMPLE_SIGN = {"normal": 0, "winding": 1}
+NR_ORDER = {"morton": 0, "shuffle": 1}
 NR_TRIMESH_FEATURE = ("face", "edge AB", "edge BC", "edge CA", "vertex A", "vertex B", "vertex C")
 # composed scenes (nr_compose_*): limits and part ops
 NR_COMPOSE_MAX_NETS, NR_COMPOSE_MAX_PARTS = 4, 16
@@ -124,6 +128,20 @@ class NRFitOpts(ctypes.Structure):
         ("clamp", ctypes.c_float),
         ("partials", ctypes.c_int),
         ("grid", ctypes.c_int),
+    ]
+
+
+class NRSampleOpts(ctypes.Structure):
+    """nr_sample_opts: the seed, counts, jitter, box and sign of nr_mesh_sample / nr_mesh_fit_samples."""
+    _fields_ = [
+        ("seed", ctypes.c_uint64),
+        ("n_surface", ctypes.c_long),
+        ("n_volume", ctypes.c_long),
+        ("sigma", ctypes.c_float),
+        ("lo", ctypes.c_float * 3),
+        ("hi", ctypes.c_float * 3),
+        ("sign", ctypes.c_int),
+        ("beta", ctypes.c_float),
     ]
 
 
@@ -311,6 +329,11 @@ def lib():
                                    ctypes.POINTER(NRStats)]),
         "nr_mesh_gbuffer": (I, [P, I, I, P, P, P, P, P, P, I, I, ctypes.POINTER(NRStats)]),
         "nr_mesh_render": (I, [P, P, I, I, I, I, ctypes.POINTER(NRStats)]),
+        "nr_mesh_area_table": (I, [P, L64, P, L64, I, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)), ctypes.POINTER(L64),
+                                   ctypes.POINTER(L64)]),
+        "nr_mesh_sample": (I, [P, ctypes.POINTER(NRSampleOpts), P, P, P, I, ctypes.POINTER(NRStats)]),
+        "nr_points_order": (I, [P, P, L64, I, FP, FP, ctypes.c_uint64, P, P, I, ctypes.POINTER(NRStats)]),
+        "nr_mesh_fit_samples": (I, [P, ctypes.POINTER(NRSampleOpts), P, P, I, ctypes.POINTER(NRStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

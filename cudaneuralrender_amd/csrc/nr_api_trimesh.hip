@@ -11,18 +11,7 @@ using namespace nr;
 // ---- triangle meshes (nr_trimesh_*; nr_trimesh_host.cpp, nr_trimesh.hip, nr_winding.hip, nr_mesh_rays.hip) ----
 // The hierarchy with its moments, the reordered triangles and the pseudonormal table are built on
 // the host at create time and live on the device; a distance query is one launch, a winding query
-// one, or two with the sdf output, a ray query (nr_mesh_rays.hip) one.
-struct nr_trimesh {
-    nr_ctx *owner = nullptr;
-    long nv = 0, nt = 0, nnodes = 0, ntl = 0;
-    int depth = 0, closed = 0;
-    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    float scale = 0;              // largest |coordinate| + largest axis extent: the boxes' slack times 2^18
-    float *d_nodes = nullptr, *d_tris = nullptr, *d_table = nullptr, *d_moments = nullptr;
-    unsigned long long *d_stats = nullptr;
-    float *d_io = nullptr;        // staging of host points and results
-    size_t cap_io = 0;
-};
+// one, or two with the sdf output, a ray query (nr_mesh_rays.hip) one.  (struct nr_trimesh: nr_ctx.h)
 
 extern "C" {
 
@@ -51,6 +40,9 @@ int nr_trimesh_create(nr_ctx *owner, const float *vertices, long nv, const int32
     m->nnodes = H.nnodes; m->ntl = H.ntl; m->depth = H.depth;
     for (int a = 0; a < 3; ++a) { m->lo[a] = H.lo[a]; m->hi[a] = H.hi[a]; }
     m->scale = std::ldexp(H.slack, TRIMESH_SLACK_SHIFT);
+    std::vector<uint32_t> area;
+    m->area_last = trimesh_area_table(H, area);
+    area.resize(std::max<size_t>(area.size(), 1), 0u);
     hipError_t e = hipSetDevice(owner->device);
     hipStream_t s = e == hipSuccess ? cur_stream(owner) : nullptr;
     if (e == hipSuccess && owner->use_own && !owner->own_stream) { delete m; return NR_E_HIP; }
@@ -58,6 +50,8 @@ int nr_trimesh_create(nr_ctx *owner, const float *vertices, long nv, const int32
     if (e == hipSuccess) e = hipMalloc(&m->d_tris, H.tris.size() * 4);
     if (e == hipSuccess) e = hipMalloc(&m->d_table, table.size() * 4);
     if (e == hipSuccess) e = hipMalloc(&m->d_moments, H.moments.size() * 4);
+    if (e == hipSuccess) e = hipMalloc(&m->d_area, area.size() * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->d_area, area.data(), area.size() * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMalloc(&m->d_stats, 128);
     if (e == hipSuccess) e = hipMemcpyAsync(m->d_nodes, H.nodes.data(), H.nodes.size() * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(m->d_tris, H.tris.data(), H.tris.size() * 4, hipMemcpyHostToDevice, s);
@@ -66,7 +60,7 @@ int nr_trimesh_create(nr_ctx *owner, const float *vertices, long nv, const int32
     if (e == hipSuccess) e = hipStreamSynchronize(s);  // (the sources are locals)
     if (e != hipSuccess) {
         const bool nomem = e == hipErrorOutOfMemory;
-        dfree(m->d_nodes); dfree(m->d_tris); dfree(m->d_table); dfree(m->d_moments); dfree(m->d_stats);
+        dfree(m->d_nodes); dfree(m->d_tris); dfree(m->d_table); dfree(m->d_moments); dfree(m->d_area); dfree(m->d_stats);
         delete m;
         return set_err(owner, nomem ? NR_E_NOMEM : NR_E_HIP, "nr_trimesh_create: %s", hipGetErrorString(e));
     }
@@ -79,7 +73,7 @@ int nr_trimesh_destroy(nr_trimesh *m) {
     nr_ctx *c = m->owner;
     (void)hipSetDevice(c->device);
     if (!(c->use_own && !c->own_stream)) (void)hipStreamSynchronize(c->stream);
-    dfree(m->d_nodes); dfree(m->d_tris); dfree(m->d_table); dfree(m->d_moments); dfree(m->d_stats); dfree(m->d_io);
+    dfree(m->d_nodes); dfree(m->d_tris); dfree(m->d_table); dfree(m->d_moments); dfree(m->d_area); dfree(m->d_stats); dfree(m->d_io);
     delete m;
     return NR_OK;
 }

@@ -113,6 +113,15 @@ struct nr_ctx {
     // value store, point words, block counts and scans), both in 8-byte words
     unsigned long long *d_spb = nullptr, *d_spa = nullptr;
     size_t cap_spb = 0, cap_spa = 0;
+    // ordering (nr_points_order; SortArgs): the two key / value buffers and the digit table, reused
+    // across calls; the staging of its host arrays; nr_mesh_fit_samples' points, sorted points,
+    // values and permutation (8 words per sample)
+    uint32_t *d_sort = nullptr;
+    size_t cap_sort = 0;
+    float *d_sortio = nullptr;
+    size_t cap_sortio = 0;
+    float *d_fitsamp = nullptr;
+    size_t cap_fitsamp = 0;
 
     // settings
     float inv_view[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 2};
@@ -154,6 +163,23 @@ struct nr_ctx {
 };
 
 struct nr_compose;
+
+// A triangle mesh on the device (nr_api_trimesh.hip creates and queries it, nr_api_sample.hip samples
+// it): the hierarchy with its moments, the reordered triangles, the pseudonormal table and the area
+// table, all built on the host at create time.
+struct nr_trimesh {
+    nr_ctx *owner = nullptr;
+    long nv = 0, nt = 0, nnodes = 0, ntl = 0;
+    int depth = 0, closed = 0;
+    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    float scale = 0;              // largest |coordinate| + largest axis extent: the boxes' slack times 2^18
+    float *d_nodes = nullptr, *d_tris = nullptr, *d_table = nullptr, *d_moments = nullptr;
+    uint32_t *d_area = nullptr;   // [ntl] thresholds of the area table (nr_mesh_sample)
+    long area_last = -1;          // its last pickable position; -1: the area sum is not > 0
+    unsigned long long *d_stats = nullptr;
+    float *d_io = nullptr;        // staging of host points and results
+    size_t cap_io = 0;
+};
 
 namespace nr {
 

@@ -274,6 +274,11 @@ struct TriBvh {
     float slack = 0;
 };
 bool trimesh_build(const float *V, long nv, const int32_t *T, long nt, int leaf, const float *table, TriBvh &out);
+// The area table of H's positions (nr_mesh_sample's triangle choice; include/neural_render.h):
+// thresholds [ntl] = min(floor(C_p / C_last 2^32), 2^32 - 1) of the running f64 area sum C, and the
+// last position whose threshold exceeds its predecessor's; -1 (thresholds all 0) when the area sum
+// is not > 0.
+long trimesh_area_table(const TriBvh &H, std::vector<uint32_t> &thresholds);
 
 // ---- camera (nr_pack.cpp; the C ABI's nr_camera) ----
 void camera_matrices(float rx, float ry, float zoom, float tx, float ty, float inv_view[12], float normal[16]);

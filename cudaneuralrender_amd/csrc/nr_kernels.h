@@ -358,6 +358,46 @@ struct MeshRayArgs {
 // normal matrix) instead of the hit record
 hipError_t launch_mesh_rays(const MeshRayArgs &R, const RenderArgs *color, int grid, hipStream_t st);
 
+// Fitting samples of a triangle mesh (nr_sample.hip k_mesh_sample; nr_mesh_sample): sample i < n_surface
+// lies on the surface, the rest in the box; every sample writes its slot of the outputs that are not NULL.
+struct SampleArgs {
+    unsigned long long seed;
+    long n_surface, n;            // n = n_surface + n_volume, 1 .. 2^27
+    float sigma;
+    float lo[3], ext[3];          // the box: lo, hi - lo
+    const float *tris;            // [ntl][12]
+    const uint32_t *thresholds;   // [ntl] (nr_internal.h trimesh_area_table)
+    int ntl, last;
+    float *points;                // [n][3]
+    int32_t *tri;                 // [n] or NULL
+    float *bary;                  // [n][3] or NULL
+};
+hipError_t launch_mesh_sample(const SampleArgs &A, int grid, hipStream_t st);  // 256-thread workgroups
+
+// The stable order of n 32-bit keys (nr_sort.hip; nr_points_order): k_sort_keys writes the keys and the
+// indices 0..n-1 into (keys[0], vals[0]); four passes of k_sort_hist, k_sort_scan, k_sort_scatter move
+// them 0 -> 1 -> 0 -> 1 -> 0, the last pass writing its indices to perm.  Every dependency between
+// workgroups is a kernel boundary.
+constexpr int SORT_TILE = 2048;       // keys per workgroup of k_sort_hist / k_sort_scatter
+constexpr int SORT_SCAN_STEP = 4096;  // table entries per step of k_sort_scan
+struct SortArgs {
+    const float *X;               // [n][3], MORTON
+    long n;                       // 1 .. 2^27
+    int mode;                     // NR_ORDER_MORTON | NR_ORDER_SHUFFLE
+    float lo[3], inv[3];          // MORTON: the box' corner, 1023.0f / (hi - lo)
+    unsigned long long seed;      // SHUFFLE
+    uint32_t *keys[2], *vals[2];  // [n] each
+    uint32_t *table;              // [256][nblk], digit-major: counts, then their exclusive scan
+    int nblk;                     // ceil(n / SORT_TILE)
+    int32_t *perm;                // [n]
+};
+inline size_t sort_scratch_words(size_t n) { return 4 * n + 256 * ((n + SORT_TILE - 1) / SORT_TILE); }
+hipError_t launch_points_order(const SortArgs &A, hipStream_t st);  // 13 launches
+constexpr int SORT_LAUNCHES = 13;
+// dst[j] = src[perm[j]] of float3 rows, and col_dst[j] = col_src[perm[j]] where col_dst is not NULL
+hipError_t launch_gather(const float *src, const float *col_src, const int32_t *perm, long n, float *dst, float *col_dst,
+                         hipStream_t st);
+
 // Composed scenes (nr_compose.hip; nr_compose_*): the distinct fp32 packs back to back in one device
 // buffer (staged into dynamic LDS in that order), the parts, and the queried rays or points.  The
 // struct travels in the kernarg segment: the part loop is wave-uniform and reads it with scalar loads.

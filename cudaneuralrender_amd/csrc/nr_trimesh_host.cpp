@@ -1,7 +1,8 @@
 // nr_trimesh_host.cpp -- the host side of the triangle-mesh queries (nr_trimesh_*): the OBJ reader
 // (nr_obj_load), the pseudonormal table (nr_trimesh_normals) and the hierarchy k_trimesh_distance
 // and k_trimesh_winding walk, with the far-field moments of every node (trimesh_build;
-// nr_mesh_hierarchy returns it).  No GPU and no HIP here: tests/cpp/trimesh_sanitize.cpp links
+// nr_mesh_hierarchy returns it), and the area table nr_mesh_sample picks triangles from
+// (trimesh_area_table; nr_mesh_area_table returns it).  No GPU and no HIP here: tests/cpp/trimesh_sanitize.cpp links
 // this file alone.  The contract is in include/neural_render.h; tests/trimesh_ref.py and
 // tests/winding_ref.py restate it in numpy.
 #include <algorithm>
@@ -401,6 +402,32 @@ bool trimesh_build(const float *V, long nv, const int32_t *T, long nt, int leaf,
     return out.depth <= bound && out.depth <= TRIMESH_STACK;
 }
 
+long trimesh_area_table(const TriBvh &H, std::vector<uint32_t> &thresholds) {
+    const long ntl = H.ntl;
+    thresholds.assign((size_t)ntl, 0u);
+    std::vector<double> C((size_t)ntl);
+    double sum = 0.0;
+    for (long k = 0; k < ntl; ++k) {
+        // |A_p| as trimesh_moments forms it
+        const float *t = H.tris.data() + (size_t)k * 12;
+        const D3 A = cross(sub(t + 4, t), sub(t + 8, t));
+        const double x = 0.5 * A.x, y = 0.5 * A.y, z = 0.5 * A.z;
+        sum += std::sqrt((x * x + y * y) + z * z);
+        C[(size_t)k] = sum;
+    }
+    if (!(sum > 0.0) || !std::isfinite(sum)) return -1;
+    long last = -1;
+    uint32_t prev = 0;
+    for (long k = 0; k < ntl; ++k) {
+        const double f = std::floor(C[(size_t)k] / sum * 4294967296.0);
+        const uint32_t T = f >= 4294967295.0 ? 0xffffffffu : (uint32_t)f;
+        thresholds[(size_t)k] = T;
+        if (T > prev) last = k;
+        prev = T;
+    }
+    return last;
+}
+
 }  // namespace nr
 
 // ---- C ABI (host only) ----
@@ -466,6 +493,32 @@ int nr_mesh_hierarchy(const float *vertices, long nv, const int32_t *triangles, 
     *nodes = n; *nnodes = H.nnodes;
     *order = o; *ntl = H.ntl;
     *moments = m; *depth = H.depth;
+    return NR_OK;
+}
+
+int nr_mesh_area_table(const float *vertices, long nv, const int32_t *triangles, long nt, int leaf, uint32_t **thresholds,
+                       long *ntl, long *last) {
+    if (thresholds) *thresholds = nullptr;
+    if (ntl) *ntl = 0;
+    if (last) *last = -1;
+    if (!vertices || !triangles || !thresholds || !ntl || !last) return nr::report_error(NR_E_INVALID, "nr_mesh_area_table: NULL argument");
+    if (nv < 1 || nv > (long)std::numeric_limits<int32_t>::max() || nt < 1 || nt > (1l << 24))
+        return nr::report_error(NR_E_INVALID, "nr_mesh_area_table: nv = %ld or nt = %ld out of range", nv, nt);
+    if (leaf < 0 || leaf > 32) return nr::report_error(NR_E_INVALID, "nr_mesh_area_table: leaf = %d outside 0..32", leaf);
+    if (!nr::trimesh_indices_ok(triangles, nt, nv)) return nr::report_error(NR_E_INVALID, "nr_mesh_area_table: a vertex index outside 0..%ld", nv - 1);
+    for (long i = 0; i < 3 * nv; ++i)
+        if (!std::isfinite(vertices[i])) return nr::report_error(NR_E_INVALID, "nr_mesh_area_table: vertex %ld is not finite", i / 3);
+    std::vector<float> table((size_t)nt * 21);
+    nr::trimesh_normals(vertices, nv, triangles, nt, table.data(), nullptr);
+    nr::TriBvh H;
+    if (!nr::trimesh_build(vertices, nv, triangles, nt, leaf > 0 ? leaf : nr::TRIMESH_LEAF_DEFAULT, table.data(), H))
+        return nr::report_error(NR_E_INVALID, "nr_mesh_area_table: a hierarchy of %d levels (the walk's stack holds %d)", H.depth, nr::TRIMESH_STACK);
+    std::vector<uint32_t> T;
+    const long l = nr::trimesh_area_table(H, T);
+    uint32_t *o = (uint32_t *)malloc(std::max<size_t>(T.size(), 1) * 4);
+    if (!o) return nr::report_error(NR_E_NOMEM, "nr_mesh_area_table: out of host memory");
+    if (!T.empty()) memcpy(o, T.data(), T.size() * 4);
+    *thresholds = o; *ntl = H.ntl; *last = l;
     return NR_OK;
 }
 

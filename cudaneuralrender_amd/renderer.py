@@ -14,6 +14,7 @@ from ._lib import (NR_AA_CONTRAST_DEFAULT, NR_AA_MODE, NR_COLOR_FACING, NR_COLOR
                    NRStats, check, lib)
 from ._lib import NR_PART_OP, NRComposeStats, NRFitOpts, NRPart
 from ._lib import NR_MESH_RAY_ANY, NR_MESH_RAY_SMOOTH, NR_TRIMESH_BRUTE
+from ._lib import NR_ORDER, NR_SAMPLE_SIGN, NRSampleOpts
 
 _FP = ctypes.POINTER(ctypes.c_float)
 
@@ -155,6 +156,30 @@ def trimesh_hierarchy(vertices, triangles, leaf=0):
         for q in (np_, mp, op):
             L.nr_free(ctypes.cast(q, ctypes.c_void_p))
     return nodes.astype(np.float32, copy=False), order.astype(np.int32, copy=False), moments.astype(np.float32, copy=False), depth.value
+
+
+def mesh_area_table(vertices, triangles, leaf=0):
+    """nr_mesh_area_table: (thresholds [ntl] uint32, last) -- the table nr_mesh_sample picks triangles
+    from, over the live triangles in trimesh_hierarchy's order, without a GPU; last = -1 for a mesh
+    without area."""
+    V, T = _mesh_arrays(vertices, triangles)
+    L = lib()
+    tp = ctypes.POINTER(ctypes.c_uint32)()
+    ntl, last = ctypes.c_long(0), ctypes.c_long(0)
+    check(L.nr_mesh_area_table(V.ctypes.data, V.shape[0], T.ctypes.data, T.shape[0], int(leaf), ctypes.byref(tp),
+                               ctypes.byref(ntl), ctypes.byref(last)))
+    try:
+        thr = np.ctypeslib.as_array(tp, shape=(ntl.value,)).copy() if ntl.value else np.zeros(0, np.uint32)
+    finally:
+        L.nr_free(ctypes.cast(tp, ctypes.c_void_p))
+    return thr.astype(np.uint32, copy=False), last.value
+
+
+def _sample_opts(seed, n_surface, n_volume, sigma, lo, hi, sign="normal", beta=0.0):
+    lo = np.broadcast_to(np.asarray(lo, np.float32), (3,))
+    hi = np.broadcast_to(np.asarray(hi, np.float32), (3,))
+    return NRSampleOpts(int(seed), int(n_surface), int(n_volume), float(sigma), (ctypes.c_float * 3)(*lo),
+                        (ctypes.c_float * 3)(*hi), NR_SAMPLE_SIGN[sign], float(beta))
 
 
 def _lattice(origin, step, dims):
@@ -865,6 +890,39 @@ class Renderer:
         self._chk(self._L.nr_layer_forward(self._ctx, layer, A.ctypes.data, Z.ctypes.data, A.shape[0], NR_HOST))
         return Z
 
+    def order_points(self, X=None, n=None, mode="morton", lo=-1.0, hi=1.0, seed=0, sorted_points=False, with_stats=False):
+        """nr_points_order on a host array X [n, 3] (mode "shuffle": X may be None, n given): perm [n] int32,
+        the stable ascending order of the points' 30-bit Morton codes in the box [lo, hi] or of the
+        seed's Philox keys -- np.argsort(keys, kind="stable") -- and with sorted_points also X[perm].
+        Needs no network."""
+        if X is not None:
+            X = np.ascontiguousarray(X, np.float32)
+            if X.ndim != 2 or X.shape[1] != 3:
+                raise ValueError(f"X must be [n, 3], got {X.shape}")
+            n = X.shape[0]
+        n = int(n)
+        lo3 = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, np.float32), (3,)))
+        hi3 = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, np.float32), (3,)))
+        perm = np.zeros(max(n, 0), np.int32)
+        out = np.zeros((max(n, 0), 3), np.float32) if sorted_points else None
+        st = NRStats()
+        self._chk(self._L.nr_points_order(self._ctx, None if X is None else X.ctypes.data, n, NR_ORDER[mode], _fptr(lo3), _fptr(hi3),
+                                          int(seed), perm.ctypes.data, out.ctypes.data if sorted_points else None, NR_HOST,
+                                          ctypes.byref(st) if with_stats else None))
+        res = (perm, out) if sorted_points else perm
+        return (res, st.as_dict()) if with_stats else res
+
+    def order_points_device(self, x_ptr, n, perm_ptr, mode="morton", lo=-1.0, hi=1.0, seed=0, sorted_ptr=None, with_stats=False):
+        """nr_points_order on device buffers (float32 X [n, 3] or None, int32 perm [n], float32 sorted [n, 3] or
+        None); runs on the renderer's stream and, without stats, returns without waiting."""
+        lo3 = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, np.float32), (3,)))
+        hi3 = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, np.float32), (3,)))
+        vp = [ctypes.c_void_p(p) if p else None for p in (x_ptr, perm_ptr, sorted_ptr)]
+        st = NRStats()
+        self._chk(self._L.nr_points_order(self._ctx, vp[0], int(n), NR_ORDER[mode], _fptr(lo3), _fptr(hi3), int(seed), vp[1],
+                                          vp[2], NR_DEVICE, ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
 
 __all__ = ["Renderer", "camera", "pack_x3", "read_keras_h5", "load_png", "save_png", "save_ppm", "save_obj", "shard_rows",
            "assemble_shards", "NR_COLOR_FACING", "NR_COLOR_MATCAP"]
@@ -1462,8 +1520,58 @@ class TriMesh:
                                           ctypes.byref(st) if with_stats else None))
         return st.as_dict() if with_stats else None
 
+    # -- fitting samples (nr_mesh_sample, nr_mesh_fit_samples)
+    def sample(self, n_surface, n_volume, seed=0, sigma=0.0, lo=-1.0, hi=1.0, tri=True, bary=True, with_stats=False):
+        """nr_mesh_sample into host arrays: {"points" [n, 3][, "tri" [n] int32, "bary" [n, 3]]} -- n_surface
+        points on the surface in proportion to triangle area (jittered by sigma times a unit-variance
+        eight-term uniform sum), then n_volume points uniform in the box [lo, hi]; tri = -1 and bary = 0
+        for those.  The bits are a function of the seed alone."""
+        n = int(n_surface) + int(n_volume)
+        out = {"points": np.zeros((max(n, 0), 3), np.float32)}
+        if tri:
+            out["tri"] = np.zeros(max(n, 0), np.int32)
+        if bary:
+            out["bary"] = np.zeros((max(n, 0), 3), np.float32)
+        opts = _sample_opts(seed, n_surface, n_volume, sigma, lo, hi)
+        st = NRStats()
+        self._chk(self._L.nr_mesh_sample(self._m, ctypes.byref(opts), out["points"].ctypes.data,
+                                         out["tri"].ctypes.data if tri else None, out["bary"].ctypes.data if bary else None,
+                                         NR_HOST, ctypes.byref(st) if with_stats else None))
+        return (out, st.as_dict()) if with_stats else out
+
+    def sample_device(self, points_ptr, n_surface, n_volume, seed=0, sigma=0.0, lo=-1.0, hi=1.0, tri_ptr=None, bary_ptr=None,
+                      with_stats=False):
+        """nr_mesh_sample into device buffers (float32 points [n, 3], int32 tri [n], float32 bary [n, 3]); runs
+        on the renderer's stream and, without stats, returns without waiting."""
+        opts = _sample_opts(seed, n_surface, n_volume, sigma, lo, hi)
+        vp = [ctypes.c_void_p(p) if p else None for p in (points_ptr, tri_ptr, bary_ptr)]
+        st = NRStats()
+        self._chk(self._L.nr_mesh_sample(self._m, ctypes.byref(opts), *vp, NR_DEVICE, ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
+    def fit_samples(self, n_surface, n_volume, seed=0, sigma=0.0, lo=-1.0, hi=1.0, sign="normal", beta=0.0, with_stats=False):
+        """nr_mesh_fit_samples into host arrays: (X [n, 3], Y [n]) -- the samples of sample(), shuffled, with
+        their signed distances (sign "normal": distance(); "winding": winding(sdf=True))."""
+        n = int(n_surface) + int(n_volume)
+        X, Y = np.zeros((max(n, 0), 3), np.float32), np.zeros(max(n, 0), np.float32)
+        opts = _sample_opts(seed, n_surface, n_volume, sigma, lo, hi, sign, beta)
+        st = NRStats()
+        self._chk(self._L.nr_mesh_fit_samples(self._m, ctypes.byref(opts), X.ctypes.data, Y.ctypes.data, NR_HOST,
+                                              ctypes.byref(st) if with_stats else None))
+        return (X, Y, st.as_dict()) if with_stats else (X, Y)
+
+    def fit_samples_device(self, x_ptr, y_ptr, n_surface, n_volume, seed=0, sigma=0.0, lo=-1.0, hi=1.0, sign="normal", beta=0.0,
+                           with_stats=False):
+        """nr_mesh_fit_samples into device buffers (float32 X [n, 3], Y [n]), ready for Fit.run_device; runs on
+        the renderer's stream and, without stats, returns without waiting."""
+        opts = _sample_opts(seed, n_surface, n_volume, sigma, lo, hi, sign, beta)
+        st = NRStats()
+        self._chk(self._L.nr_mesh_fit_samples(self._m, ctypes.byref(opts), ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr),
+                                              NR_DEVICE, ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
     # -- rays (nr_mesh_trace_rays, nr_mesh_gbuffer, nr_mesh_render)
-    _RAY_KEYS = ("status", "t", "tri", "bary", "position", "normal")
+    _RAY_KEYS =("status", "t", "tri", "bary", "position", "normal")
 
     @staticmethod
     def _ray_flags(smooth, any_hit, brute):

@@ -747,7 +747,8 @@ int nr_fit_weights(nr_fit *f, float *params /*[P], host*/, long *step);
  *  - nr_trimesh_distance: any of sdf [n], closest [n][3], tri [n], feature [n] may be NULL; loc =
  *    NR_HOST or NR_DEVICE for X and all of them.  One launch; with loc = NR_DEVICE and no stats the
  *    call only enqueues.  Points are taken 64 at a time in the order given and the 64 share one walk:
- *    points that are neighbours in space should be neighbours in X (the call does not sort).
+ *    points that are neighbours in space should be neighbours in X (the call does not sort;
+ *    nr_points_order, below, gives the order).
  *    stats (may be NULL): ray_steps = n, shade_evals = point-triangle evaluations done (summed over
  *    the points), launches, ms_total; everything else 0.
  *  - nr_trimesh_info: any output may be NULL; lo, hi = the vertices' bound (not grown); nodes and
@@ -825,7 +826,7 @@ int nr_fit_weights(nr_fit *f, float *params /*[P], host*/, long *step);
  *    left as it is: two launches on the stream, nothing read back between them.  With loc = NR_DEVICE
  *    and no stats the call only enqueues.  Points are taken 64 at a time in the order given and the
  *    64 share one walk, the union of their cuts through the tree: neighbours in space should be
- *    neighbours in X (the call does not sort).  stats: ray_steps = n, shade_evals = solid angles and
+ *    neighbours in X (the call does not sort; nr_points_order does).  stats: ray_steps = n, shade_evals = solid angles and
  *    expansions evaluated, summed over the points (plus the distance launch's evaluations with sdf),
  *    launches, ms_total.
  * Errors of nr_mesh_winding: as nr_trimesh_distance, and NR_E_INVALID for a beta that is negative
@@ -938,6 +939,99 @@ int nr_mesh_trace_rays(nr_trimesh *m, const float *origins /*[n][3]*/, const flo
 int nr_mesh_gbuffer(nr_trimesh *m, int W, int H, int32_t *status, float *t, int32_t *tri, float *bary,
                     float *position, float *normal, int flags, int loc, nr_stats *stats);
 int nr_mesh_render(nr_trimesh *m, uint32_t *out /*[H][W]*/, int W, int H, int flags, int out_loc, nr_stats *stats);
+
+/* ---- triangle meshes: fitting samples, drawn, ordered and labelled on the device ------- */
+/* (new symbols only: NR_ABI_VERSION stays 3, nr_stats is unchanged)
+ * The stage between a mesh and nr_fit_run: nr_mesh_sample draws seeded points on the surface of a
+ * nr_trimesh (in proportion to triangle area, optionally jittered) and in a box; nr_points_order gives
+ * the Morton order or a seeded shuffle of any point set, by a stable sort on the device;
+ * nr_mesh_fit_samples runs draw -> Morton order -> signed distance -> shuffle in one call and leaves
+ * X [n][3], Y [n] for nr_fit_run, nothing read back.  Every bit is fixed by this text -- integers,
+ * and the f32 operations named, one rounding each, no transcendental function -- and
+ * tests/sample_ref.py restates it in numpy.
+ *
+ *  1. Random numbers: Philox4x32-10 (Salmon et al. 2011, Random123) with key (k0, k1) = (seed low 32,
+ *     seed high 32) and counter (c0, c1, c2, c3) = (i low 32, i high 32, stream, 0), i the sample's index
+ *     in the output.  Ten rounds of
+ *       p0 = 0xD2511F53 * c0,  p1 = 0xCD9E8D57 * c2                      (64-bit products)
+ *       (c0, c1, c2, c3) = (hi(p1) ^ c1 ^ k0, lo(p1), hi(p0) ^ c3 ^ k1, lo(p0))
+ *       k0 += 0x9E3779B9,  k1 += 0xBB67AE85                               (mod 2^32)
+ *     give the words w0..w3.  Known answers: zero counter and key -> 6627e8d5 e169c58d bc57ac4c
+ *     9b00dbd8; all-ones counter and key -> 408f276d 41c83b0e a20bc7c6 6d5451fd.  Streams: 0 draws the
+ *     sample, 1, 2, 3 jitter x, y, z, 4 is the shuffle key.
+ *  2. The area table (built by nr_trimesh_create on the host; nr_mesh_area_table returns it without a
+ *     device, from the same code) over the live triangles in position order, nr_mesh_hierarchy's
+ *     `order` -- neighbours in the table are neighbours in space.  In f64 from the f32 corners, as the
+ *     moments above:  |A_p| = sqrt((A.x A.x + A.y A.y) + A.z A.z),  A = 0.5 ((b - a) x (c - a));
+ *     C_p = the sequential running sum of |A_p|;  T_p = min(floor(C_p / C_last * 2^32), 2^32 - 1) as
+ *     uint32;  L = the last position whose T exceeds its predecessor's (T_-1 = 0).  If C_last is not
+ *     > 0 (no live triangle) every T is 0 and L = -1.
+ *  3. Surface samples, i < n_surface.  Position p = min(#{q : T_q <= w0}, L): a triangle is picked
+ *     with probability (T_p - T_p-1) / 2^32, a triangle of zero share never.  tri = order[p].  With
+ *     (a, b, c) the triangle's corners:  iu = w1 >> 8, iv = w2 >> 8;  if iu + iv > 2^24 then
+ *     iu = 2^24 - iu, iv = 2^24 - iv;  u = iu 2^-24, v = iv 2^-24 (exact);  e1 = b - a, e2 = c - a (f32);
+ *       point_k = fmaf(v, e2_k, fmaf(u, e1_k, a_k))  per axis k,
+ *       bary = ((2^24 - iu - iv) 2^-24, u, v).
+ *  4. Jitter, when sigma > 0, of the surface samples only: for axis k, S = the sum of the eight 16-bit
+ *     halves of the four words of stream 1 + k;  g = (float)(S - 262140) * c, c the f32 with bits
+ *     0x379cc471 (sqrt(1.5) / 65536);  point_k = fmaf(sigma, g, point_k).  g is a sum of eight uniform
+ *     terms, not a normal deviate: mean 0, variance 1, support about +-4.9, and exact in integers up
+ *     to one product, which no inverse-CDF or Box-Muller deviate would be; eight terms are close
+ *     enough to a bell to smear a surface.  tri and bary stay those of the point before the jitter.
+ *  5. Volume samples, i >= n_surface: point_k = fmaf((float)(w_k >> 8) * 2^-24, hi_k - lo_k, lo_k) with
+ *     the words of stream 0 and hi_k - lo_k one f32 subtraction; tri = -1, bary = 0.
+ *  6. Order keys.  NR_ORDER_MORTON: inv_k = 1023.0f / (hi_k - lo_k) in f32;  t = (x_k - lo_k) * inv_k;
+ *     q_k = 1023 if t >= 1023, else (int)t if t > 0, else 0 (so a NaN gives 0, a point outside the box
+ *     its nearest cell);  key = the 30-bit interleave of q, x in bit 0, y in bit 1, z in bit 2, and so on.
+ *     NR_ORDER_SHUFFLE: key = w0 of stream 4 at counter i; X may be NULL (and sorted then too).
+ *  7. perm = the stable ascending sort of the keys, ties by index -- numpy's argsort(key,
+ *     kind="stable") -- and sorted[j] = X[perm[j]].  n in [1, 2^27].  (Equal shuffle keys are rare but
+ *     possible; the tie rule keeps perm a permutation and a function of the seed.)
+ *  8. nr_mesh_fit_samples = bit for bit, with n = n_surface + n_volume <= 2^27:  nr_mesh_sample into
+ *     scratch;  nr_points_order MORTON with the box lo / hi;  nr_trimesh_distance (sign =
+ *     NR_SAMPLE_SIGN_NORMAL) or nr_mesh_winding's sdf output with beta (NR_SAMPLE_SIGN_WINDING) of the
+ *     sorted points;  nr_points_order SHUFFLE with the same seed;  X and Y = the sorted points and
+ *     their values gathered by that permutation.  The distance's winner is a minimum and a point's
+ *     winding sum does not depend on the other points, so Y does not depend on the order it was
+ *     computed in: the Morton order is there for speed only (the 64 points of a walk are neighbours).
+ *
+ *  - nr_mesh_area_table (host only, no device): thresholds [ntl], the caller's to nr_free; last = L.
+ *  - nr_mesh_sample: points [n][3], tri [n] or NULL, bary [n][3] or NULL; loc for all three.  One
+ *    launch; with loc = NR_DEVICE and no stats the call only enqueues.  stats: ray_steps = n, launches,
+ *    ms_total.  NR_E_STATE: n_surface > 0 on a mesh whose area sum is not > 0 (creating one works).
+ *  - nr_points_order: perm [n] int32, sorted [n][3] or NULL; loc for X, perm and sorted; lo and hi are
+ *    read in MORTON mode only, seed in SHUFFLE mode only.  The sort is a least-significant-digit radix
+ *    sort of four 8-bit passes (count, scan, scatter: 13 launches, 14 with sorted) in which no
+ *    workgroup waits on another; scratch, 16 bytes per point and 1 KiB per 2048 points, is held by the
+ *    context and reused.  stats: ray_steps = n, launches, ms_total.
+ *  - nr_mesh_fit_samples: X [n][3], Y [n]; loc for both.  stats: ray_steps = n, shade_evals = the
+ *    query's evaluations, launches, ms_total.  Scratch of 48 bytes per sample is held by the context.
+ * Errors: as nr_trimesh_distance (a NULL mesh, ctx or output, NR_E_HIP, NR_E_NOMEM), and NR_E_INVALID
+ * for a NULL opts, a negative count, n = 0 or n > 2^27, a sigma that is negative or not finite, a box
+ * with hi_k <= lo_k or an edge that is not finite, an unknown mode or sign, a beta that is negative
+ * or not finite, X NULL in MORTON mode, sorted without X. */
+typedef struct nr_sample_opts {
+    uint64_t seed;
+    long n_surface;      /* points on the surface, area-weighted, first in the output */
+    long n_volume;       /* points uniform in the box [lo, hi], after them */
+    float sigma;         /* jitter of the surface points, >= 0; 0 = none */
+    float lo[3], hi[3];  /* the box: volume points, and the Morton quantisation of nr_mesh_fit_samples */
+    int sign;            /* nr_mesh_fit_samples: NR_SAMPLE_SIGN_NORMAL or NR_SAMPLE_SIGN_WINDING */
+    float beta;          /* for WINDING, 0 = 2.0 */
+} nr_sample_opts;
+#define NR_SAMPLE_SIGN_NORMAL  0  /* nr_trimesh_distance's sign (the pseudonormal's) */
+#define NR_SAMPLE_SIGN_WINDING 1  /* nr_mesh_winding's sdf output */
+#define NR_ORDER_MORTON  0
+#define NR_ORDER_SHUFFLE 1
+int nr_mesh_area_table(const float *vertices /*[nv][3]*/, long nv, const int32_t *triangles /*[nt][3]*/, long nt,
+                       int leaf /*0 = 8, else 1..32*/, uint32_t **thresholds /*[ntl]*/, long *ntl, long *last);
+int nr_mesh_sample(nr_trimesh *m, const nr_sample_opts *opts, float *points /*[n][3]*/, int32_t *tri /*[n] or NULL*/,
+                   float *bary /*[n][3] or NULL*/, int loc, nr_stats *stats);
+int nr_points_order(nr_ctx *ctx, const float *X /*[n][3] or NULL*/, long n, int mode, const float lo[3],
+                    const float hi[3], uint64_t seed, int32_t *perm /*[n]*/, float *sorted /*[n][3] or NULL*/,
+                    int loc, nr_stats *stats);
+int nr_mesh_fit_samples(nr_trimesh *m, const nr_sample_opts *opts, float *X /*[n][3]*/, float *Y /*[n]*/, int loc,
+                        nr_stats *stats);
 
 /* ---- composed scenes: several networks, placed and combined by CSG ---------------- */
 /* (new symbols and new structs only: NR_ABI_VERSION stays 3, nr_stats is unchanged)

@@ -13,6 +13,8 @@ of a closed one.  A [3, 32 x 4, 1]
 student, batch 2^16, lr 1e-3, --epochs epochs; then load_into a renderer and a 256^2 frame, whose
 silhouette is compared with the mesh's own (TriMesh.gbuffer through the same camera) and, when the
 mesh came from a network, with that network's.
+--sampler device replaces the torch recipe by one nr_mesh_fit_samples call: half the points on the surface in
+proportion to triangle area at sigma 0.03, half uniform in the box [-1.3, 1.3]^3.
 Runs on the GPU box: python3 tools/fit_mesh.py [mesh.obj]"""
 import argparse
 import os
@@ -36,6 +38,8 @@ def main():
     ap.add_argument("--epochs", type=int, default=400)
     ap.add_argument("--out", help="write the student's frame here (.png)")
     ap.add_argument("--sign", choices=("normal", "winding"), help="default: normal for a closed mesh, winding otherwise")
+    ap.add_argument("--sampler", choices=("torch", "device"), default="torch",
+                    help="torch: the recipe above (the recorded numbers); device: one nr_mesh_fit_samples call")
     ap.add_argument("--drop-x", type=float, nargs=2, metavar=("LO", "HI"), help="remove the triangles whose centroid has LO <= x <= HI")
     args = ap.parse_args()
     n = args.points
@@ -81,27 +85,42 @@ def main():
         sm = gb["status"] == 2  # NR_RAY_HIT
         print(f"mesh at 256^2: {int(sm.sum())} px in {gst['ms_total']:.2f} ms ({gst['shade_evals'] / sm.size:.1f} ray-triangle "
               f"evaluations per pixel)")
-        d = torch.randn((n // 2, 3), generator=gen, device=dev)
-        u = torch.rand((n // 2, 1), generator=gen, device=dev)
-        ball = (d / d.norm(dim=1, keepdim=True) * 1.2 * u.pow(1.0 / 3.0)).float()
-        ball = ball[morton_order(ball, -1.3, 1.3)].contiguous()
-        surf = torch.zeros_like(ball)
-        torch.cuda.synchronize()
-        st0 = m.distance_device(ball.data_ptr(), n // 2, closest_ptr=surf.data_ptr(), with_stats=True)
-        surf = surf + 0.03 * torch.randn(surf.shape, generator=gen, device=dev)
-        X = torch.cat([ball, surf])
-        X = X[morton_order(X, -1.3, 1.3)].float().contiguous()
-        Y = torch.zeros(n, dtype=torch.float32, device=dev)
-        torch.cuda.synchronize()
-        if sign == "winding":
-            st1 = m.winding_device(X.data_ptr(), n, sdf_ptr=Y.data_ptr(), with_stats=True)
+        if args.sampler == "device":
+            # half on the surface in proportion to area, jittered by 0.03, half uniform in the box: drawn, ordered,
+            # labelled and shuffled by the library, left on the device
+            X = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+            Y = torch.zeros(n, dtype=torch.float32, device=dev)
+            torch.cuda.synchronize()
+            st1 = m.fit_samples_device(X.data_ptr(), Y.data_ptr(), n // 2, n - n // 2, seed=5, sigma=0.03, lo=-1.3, hi=1.3,
+                                       sign=sign, with_stats=True)
         else:
-            st1 = m.distance_device(X.data_ptr(), n, Y.data_ptr(), with_stats=True)
-    print(f"samples: {n // 2} ball points -> closest points in {st0['ms_total']:.2f} ms ({st0['shade_evals'] / (n // 2):.1f} "
-          f"evaluations per point); {n} signed distances (sign: {sign}) in {st1['ms_total']:.2f} ms ({st1['shade_evals'] / n:.1f} per point); "
-          f"{float((Y < 0).float().mean()):.4f} of them inside, |Y| < clamp at {float((Y.abs() < CLAMP).float().mean()):.3f}")
-    perm = torch.randperm(n, generator=gen, device=dev)
-    X, Y = X[perm].contiguous(), Y[perm].contiguous()
+            d = torch.randn((n // 2, 3), generator=gen, device=dev)
+            u = torch.rand((n // 2, 1), generator=gen, device=dev)
+            ball = (d / d.norm(dim=1, keepdim=True) * 1.2 * u.pow(1.0 / 3.0)).float()
+            ball = ball[morton_order(ball, -1.3, 1.3)].contiguous()
+            surf = torch.zeros_like(ball)
+            torch.cuda.synchronize()
+            st0 = m.distance_device(ball.data_ptr(), n // 2, closest_ptr=surf.data_ptr(), with_stats=True)
+            surf = surf + 0.03 * torch.randn(surf.shape, generator=gen, device=dev)
+            X = torch.cat([ball, surf])
+            X = X[morton_order(X, -1.3, 1.3)].float().contiguous()
+            Y = torch.zeros(n, dtype=torch.float32, device=dev)
+            torch.cuda.synchronize()
+            if sign == "winding":
+                st1 = m.winding_device(X.data_ptr(), n, sdf_ptr=Y.data_ptr(), with_stats=True)
+            else:
+                st1 = m.distance_device(X.data_ptr(), n, Y.data_ptr(), with_stats=True)
+    if args.sampler == "device":
+        print(f"samples: nr_mesh_fit_samples, {n // 2} surface points (area-weighted, sigma 0.03) and {n - n // 2} in the box "
+              f"[-1.3, 1.3]^3: drawn, Morton-ordered, {n} signed distances (sign: {sign}) and shuffled in {st1['ms_total']:.2f} ms "
+              f"({st1['shade_evals'] / n:.1f} evaluations per point); "
+              f"{float((Y < 0).float().mean()):.4f} of them inside, |Y| < clamp at {float((Y.abs() < CLAMP).float().mean()):.3f}")
+    else:
+        print(f"samples: {n // 2} ball points -> closest points in {st0['ms_total']:.2f} ms ({st0['shade_evals'] / (n // 2):.1f} "
+              f"evaluations per point); {n} signed distances (sign: {sign}) in {st1['ms_total']:.2f} ms ({st1['shade_evals'] / n:.1f} per point); "
+              f"{float((Y < 0).float().mean()):.4f} of them inside, |Y| < clamp at {float((Y.abs() < CLAMP).float().mean()):.3f}")
+        perm = torch.randperm(n, generator=gen, device=dev)
+        X, Y = X[perm].contiguous(), Y[perm].contiguous()
 
     dims, K, B = init_net(3, 20)
     batch = 1 << 16
