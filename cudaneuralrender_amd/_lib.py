@@ -54,6 +54,7 @@ EXPORTS = [
     "nr_trimesh_distance", "nr_mesh_hierarchy", "nr_mesh_winding",
     "nr_mesh_trace_rays", "nr_mesh_gbuffer", "nr_mesh_render",
     "nr_mesh_area_table", "nr_mesh_sample", "nr_points_order", "nr_mesh_fit_samples",
+    "nr_mesh_sample_grid", "nr_mesh_remesh", "nr_mesh_remesh_sparse",
 ]
 # nr_trimesh_distance: flags, and the feature codes of its `feature` output
 NR_TRIMESH_BRUTE = 1
@@ -334,6 +335,11 @@ def lib():
         "nr_mesh_sample": (I, [P, ctypes.POINTER(NRSampleOpts), P, P, P, I, ctypes.POINTER(NRStats)]),
         "nr_points_order": (I, [P, P, L64, I, FP, FP, ctypes.c_uint64, P, P, I, ctypes.POINTER(NRStats)]),
         "nr_mesh_fit_samples": (I, [P, ctypes.POINTER(NRSampleOpts), P, P, I, ctypes.POINTER(NRStats)]),
+        "nr_mesh_sample_grid": (I, [P, FP, FP, IP, I, F, I, P, I, ctypes.POINTER(NRStats)]),
+        "nr_mesh_remesh": (I, [P, FP, FP, IP, F, I, F, P, P, L64, P, L64, ctypes.POINTER(L64), ctypes.POINTER(L64), I,
+                                  ctypes.POINTER(NRStats)]),
+        "nr_mesh_remesh_sparse": (I, [P, FP, FP, IP, F, I, F, I, F, P, P, P, L64, P, L64, ctypes.POINTER(L64),
+                                         ctypes.POINTER(L64), ctypes.POINTER(L64), I, ctypes.POINTER(NRStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -61,11 +61,12 @@ int lattice_check(nr_ctx *c, const char *fn, const float *origin, const float *s
 
 // Count, scan and (with output buffers of sufficient capacity) emit over the device lattice d_sdf;
 // with `normals` the vertex normals too.  cp: the lattice holds the composed field of cp (whose owner
-// is c): the normals are that field's and `part` (may be NULL) gets the vertices' owners.  *launches
-// counts the kernels issued.
+// is c): the normals are that field's and `part` (may be NULL) gets the vertices' owners.  field: the
+// lattice holds that field: no normals, and `part` (may be NULL) gets its labels.  *launches counts
+// the kernels issued.
 int mesh_run(nr_ctx *c, const char *fn, hipStream_t s, const LatticeArgs &L, const float *d_sdf, float iso,
                     float *vertices, float *normals, long v_cap, int32_t *triangles, long t_cap, long *nv, long *nt,
-                    int loc, int *launches, nr_compose *cp, int32_t *part) {
+                    int loc, int *launches, nr_compose *cp, int32_t *part, const FieldSource *field) {
     const size_t N = (size_t)L.n;
     const size_t nblk = (N + 255) / 256;
     // scratch, in 8-byte words: totals [2], scans [2][nblk], block counts [2][nblk] u32, point words [N] u32
@@ -106,7 +107,9 @@ int mesh_run(nr_ctx *c, const char *fn, hipStream_t s, const LatticeArgs &L, con
     A.triangles = dt;
     HIPCHK(c, launch_mesh_emit(A, s));
     *launches += 1;
-    if (cp) {
+    if (field) {
+        if (dp && (rc = field->label(field->self, dv, dp, NV, s, launches)) != NR_OK) return rc;
+    } else if (cp) {
         if (dn || dp) {
             if ((rc = compose_vertex_pass(cp, dv, dn, dp, NV, s)) != NR_OK) return rc;
             *launches += 1;
@@ -131,11 +134,12 @@ int mesh_run(nr_ctx *c, const char *fn, hipStream_t s, const LatticeArgs &L, con
 
 // nr_extract_mesh_sparse on c's stream and scratch.  cp == NULL: c's network and scene.  cp: the
 // composed field of cp (whose owner is c) in the two samplers and the vertex pass, which then
-// writes `part` too (may be NULL); the caller has zeroed cp's statistics.  timed: *done gets ms.
+// writes `part` too (may be NULL); the caller has zeroed cp's statistics.  field (cp == NULL): that
+// field in the two samplers, and its labels into `part` (may be NULL; no normals).  timed: *done gets ms.
 int sparse_run(nr_ctx *c, nr_compose *cp, const char *fn, const float origin[3], const float step[3], const int dims[3],
                       float iso, int brick, float band, float *vertices, float *normals, int32_t *part, int64_t *keys,
                       long v_cap, int32_t *triangles, long t_cap, long *nv, long *nt, long *active_bricks, int loc, bool timed,
-                      SparseDone *done) {
+                      SparseDone *done, const FieldSource *field) {
     if (!origin || !step || !dims || !nv || !nt) return set_err(c, NR_E_INVALID, "%s: NULL origin, step, dims, nv or nt", fn);
     *nv = 0;
     *nt = 0;
@@ -157,7 +161,7 @@ int sparse_run(nr_ctx *c, nr_compose *cp, const char *fn, const float origin[3],
     const unsigned long long nbricks = (unsigned long long)L.nbx * L.nby * L.nbz;
     if (nbricks > (1ull << 30)) return set_err(c, NR_E_INVALID, "%s: %llu bricks, more than 2^30", fn, nbricks);
     int rc;
-    if (!cp && (rc = fused_check(c, fn)) != NR_OK) return rc;
+    if (!cp && !field && (rc = fused_check(c, fn)) != NR_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     GET_STREAM(c, s);
     L.nbricks = (uint32_t)nbricks;
@@ -186,7 +190,11 @@ int sparse_run(nr_ctx *c, nr_compose *cp, const char *fn, const float origin[3],
     A.map = reinterpret_cast<int32_t *>(c->d_spb + 2 + 3 * nblk_b);
     A.coarse = reinterpret_cast<float *>(c->d_spb + 2 + 3 * nblk_b + ((size_t)L.nbricks + 1) / 2);
     HIPCHK(c, hipEventRecord(c->ev0, s));
-    if (cp) {
+    int launches = 3;  // a sampler's one launch, the classification, its scan
+    if (field) {
+        launches -= 1;
+        if ((rc = field->sample(field->self, A, false, s, &launches)) != NR_OK) return rc;
+    } else if (cp) {
         if ((rc = compose_sparse_sampler(cp, A, false, s)) != NR_OK) return rc;
     } else {
         HIPCHK(c, launch_sparse_coarse(A, c->mlp16, persistent_grid(c, L.ncoarse, 256, 12), s));  // as nr_sample_grid
@@ -195,7 +203,6 @@ int sparse_run(nr_ctx *c, nr_compose *cp, const char *fn, const float origin[3],
     MeshArgs scan{};
     scan.nblk = A.nblk_b; scan.cnt = A.bcnt; scan.off = A.boff; scan.total = A.btotal;
     HIPCHK(c, launch_mesh_scan(scan, s));
-    int launches = 3;
     unsigned long long btot[2] = {0, 0};
     HIPCHK(c, hipMemcpyAsync(btot, A.btotal, sizeof btot, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
@@ -221,7 +228,10 @@ int sparse_run(nr_ctx *c, nr_compose *cp, const char *fn, const float origin[3],
         A.word = reinterpret_cast<uint32_t *>(c->d_spa + 2 + 3 * nblk_m + ((size_t)A.nactive + 1) / 2);
         A.store = reinterpret_cast<float *>(A.word + npts);
         HIPCHK(c, launch_sparse_classify_emit(A, s));
-        if (cp) {
+        if (field) {
+            launches -= 1;
+            if ((rc = field->sample(field->self, A, true, s, &launches)) != NR_OK) return rc;
+        } else if (cp) {
             if ((rc = compose_sparse_sampler(cp, A, true, s)) != NR_OK) return rc;
         } else {
             HIPCHK(c, launch_sparse_sample(A, c->mlp16, persistent_grid(c, npts, 256, 12), s));
@@ -253,7 +263,9 @@ int sparse_run(nr_ctx *c, nr_compose *cp, const char *fn, const float origin[3],
         A.triangles = dt;
         HIPCHK(c, launch_sparse_mesh_emit(A, s));
         launches += 1;
-        if (cp) {
+        if (field) {
+            if (dp && (rc = field->label(field->self, dv, dp, NV, s, &launches)) != NR_OK) return rc;
+        } else if (cp) {
             if (dn || dp) {
                 if ((rc = compose_vertex_pass(cp, dv, dn, dp, NV, s)) != NR_OK) return rc;
                 launches += 1;

@@ -192,6 +192,207 @@ int nr_mesh_winding(nr_trimesh *m, const float *X, long n, float beta, float *wi
 
 }  // extern "C"
 
+// ---- the mesh's signed distance on a lattice, remeshed (nr_trimesh_grid.hip; mesh_run and sparse_run: nr_api_mesh.hip) ----
+// The values are the point calls': k_trimesh_grid_distance and, for the winding sign, the
+// k_trimesh_grid_winding launch that signs them in place.  The lattice, the extraction's scratch and
+// the staging of a host mesh are the owner context's, as for nr_extract_mesh.
+
+namespace {
+
+struct GridField {
+    nr_trimesh *m;
+    int sign, brute;
+    float beta;
+};
+
+int grid_check(nr_ctx *c, const char *fn, int sign, float beta, int flags) {
+    if (sign != NR_SAMPLE_SIGN_NORMAL && sign != NR_SAMPLE_SIGN_WINDING) return set_err(c, NR_E_INVALID, "%s: unknown sign %d", fn, sign);
+    if (!std::isfinite(beta) || beta < 0.0f) return set_err(c, NR_E_INVALID, "%s: beta = %g is negative or not finite", fn, (double)beta);
+    if (flags & ~NR_TRIMESH_BRUTE) return set_err(c, NR_E_INVALID, "%s: unknown flag bits %#x", fn, flags);
+    return NR_OK;
+}
+
+// the two launches' arguments for values into d_sdf
+void grid_args(const GridField &F, float *d_sdf, TriMeshArgs &D, TriWindArgs &W) {
+    const nr_trimesh *m = F.m;
+    D = TriMeshArgs{};
+    D.nodes = m->d_nodes; D.tris = m->d_tris; D.table = m->d_table;
+    D.nnodes = (int)m->nnodes; D.ntl = (int)m->ntl;
+    D.brute = F.brute;
+    D.sdf = d_sdf;
+    D.stats = m->d_stats;
+    W = TriWindArgs{};
+    W.nodes = m->d_nodes; W.tris = m->d_tris; W.moments = m->d_moments;
+    W.nnodes = D.nnodes; W.ntl = D.ntl;
+    W.brute = F.brute;
+    W.beta = F.beta == 0.0f ? 2.0f : F.beta;
+    W.sdf = d_sdf;
+    W.stats = m->d_stats;
+}
+
+int grid_dense(const GridField &F, const LatticeArgs &L, float *d_sdf, hipStream_t s, int *launches) {
+    nr_ctx *c = F.m->owner;
+    TriMeshArgs D;
+    TriWindArgs W;
+    grid_args(F, d_sdf, D, W);
+    const bool wind = F.sign == NR_SAMPLE_SIGN_WINDING;
+    HIPCHK(c, launch_trimesh_lattice(D, wind ? &W : nullptr, L, num_cus(c->device), s));
+    *launches += wind ? 2 : 1;
+    return NR_OK;
+}
+
+// FieldSource::sample
+int grid_sparse(void *self, const SparseArgs &A, bool store, hipStream_t s, int *launches) {
+    const GridField &F = *static_cast<const GridField *>(self);
+    nr_ctx *c = F.m->owner;
+    TriMeshArgs D;
+    TriWindArgs W;
+    grid_args(F, store ? A.store : A.coarse, D, W);
+    const bool wind = F.sign == NR_SAMPLE_SIGN_WINDING;
+    HIPCHK(c, launch_trimesh_sparse(D, wind ? &W : nullptr, A, store, num_cus(c->device), s));
+    *launches += wind ? 2 : 1;
+    return NR_OK;
+}
+
+// FieldSource::label: source_tri, nr_trimesh_distance's tri of the device vertices by its own launch
+int grid_label(void *self, const float *d_vertices, int32_t *d_label, size_t nv, hipStream_t s, int *launches) {
+    const GridField &F = *static_cast<const GridField *>(self);
+    const nr_trimesh *m = F.m;
+    nr_ctx *c = m->owner;
+    TriMeshArgs D{};
+    D.X = d_vertices; D.n = (long)nv;
+    D.nodes = m->d_nodes; D.tris = m->d_tris; D.table = m->d_table;
+    D.nnodes = (int)m->nnodes; D.ntl = (int)m->ntl;
+    D.tri = d_label;
+    D.stats = m->d_stats;
+    const size_t chunks = (nv + 63) / 64;
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((chunks + 3) / 4, (size_t)num_cus(c->device) * 8));
+    HIPCHK(c, launch_trimesh_distance(D, grid, s));
+    *launches += 1;
+    return NR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nr_mesh_sample_grid(nr_trimesh *m, const float origin[3], const float step[3], const int dims[3], int sign, float beta,
+                           int flags, float *sdf, int loc, nr_stats *stats) {
+    const char *fn = "nr_mesh_sample_grid";
+    if (!m) return set_err(nullptr, NR_E_INVALID, "%s: mesh is NULL", fn);
+    nr_ctx *c = m->owner;
+    if (!sdf) return set_err(c, NR_E_INVALID, "%s: sdf is NULL", fn);
+    int rc;
+    if ((rc = lattice_check(c, fn, origin, step, dims, 1)) != NR_OK) return rc;
+    if ((rc = grid_check(c, fn, sign, beta, flags)) != NR_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const LatticeArgs L = make_lattice(origin, step, dims);
+    const size_t N = (size_t)L.n;
+    float *d = sdf;
+    if (loc != NR_DEVICE) {
+        if ((rc = ensure_buf(c, c->d_grid, c->cap_grid, N)) != NR_OK) return rc;
+        d = c->d_grid;
+    }
+    const GridField F{m, sign, (flags & NR_TRIMESH_BRUTE) != 0, beta};
+    nr_stats st{};
+    int launches = 1;  // the counter's memset
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, hipMemsetAsync(m->d_stats, 0, 8, s));
+    if ((rc = grid_dense(F, L, d, s, &launches)) != NR_OK) return rc;
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (loc != NR_DEVICE) HIPCHK(c, hipMemcpyAsync(sdf, d, N * 4, hipMemcpyDeviceToHost, s));
+    unsigned long long evals = 0;
+    if (stats) HIPCHK(c, hipMemcpyAsync(&evals, m->d_stats, 8, hipMemcpyDeviceToHost, s));
+    rc = end_timed(c, stats != nullptr, loc, s, &st.ms_total);
+    if (rc != NR_OK || !stats) return rc;
+    st.ray_steps = (uint64_t)N;
+    st.shade_evals = evals;
+    st.launches = launches;
+    *stats = st;
+    return NR_OK;
+}
+
+int nr_mesh_remesh(nr_trimesh *m, const float origin[3], const float step[3], const int dims[3], float iso, int sign,
+                      float beta, float *vertices, int32_t *source_tri, long v_cap, int32_t *triangles, long t_cap, long *nv,
+                      long *nt, int loc, nr_stats *stats) {
+    const char *fn = "nr_mesh_remesh";
+    if (!m) return set_err(nullptr, NR_E_INVALID, "%s: mesh is NULL", fn);
+    nr_ctx *c = m->owner;
+    if (!nv || !nt) return set_err(c, NR_E_INVALID, "%s: NULL nv or nt", fn);
+    *nv = 0;
+    *nt = 0;
+    int rc;
+    if ((rc = lattice_check(c, fn, origin, step, dims, 2)) != NR_OK) return rc;
+    if ((rc = grid_check(c, fn, sign, beta, 0)) != NR_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const LatticeArgs L = make_lattice(origin, step, dims);
+    if ((rc = ensure_buf(c, c->d_grid, c->cap_grid, (size_t)L.n)) != NR_OK) return rc;
+    GridField F{m, sign, 0, beta};
+    const FieldSource field{&F, grid_sparse, grid_label};
+    int launches = 1;  // the counter's memset
+    HIPCHK(c, hipEventRecord(c->ev0, s));
+    HIPCHK(c, hipMemsetAsync(m->d_stats, 0, 8, s));
+    if ((rc = grid_dense(F, L, c->d_grid, s, &launches)) != NR_OK) return rc;
+    rc = mesh_run(c, fn, s, L, c->d_grid, iso, vertices, nullptr, v_cap, triangles, t_cap, nv, nt, loc, &launches, nullptr,
+                  vertices && triangles ? source_tri : nullptr, &field);
+    if (rc != NR_OK) return rc;
+    HIPCHK(c, hipEventRecord(c->ev1, s));
+    if (stats) {
+        unsigned long long evals = 0;
+        HIPCHK(c, hipMemcpyAsync(&evals, m->d_stats, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        nr_stats st{};
+        st.ray_steps = (uint64_t)L.n;
+        st.rays_shaded = (uint64_t)*nv;
+        st.shade_evals = evals;
+        st.launches = launches;
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        st.ms_total = ms;
+        *stats = st;
+    }
+    return NR_OK;
+}
+
+int nr_mesh_remesh_sparse(nr_trimesh *m, const float origin[3], const float step[3], const int dims[3], float iso, int sign,
+                             float beta, int brick, float band, float *vertices, int32_t *source_tri, int64_t *keys,
+                             long v_cap, int32_t *triangles, long t_cap, long *nv, long *nt, long *active_bricks, int loc,
+                             nr_stats *stats) {
+    const char *fn = "nr_mesh_remesh_sparse";
+    if (!m) return set_err(nullptr, NR_E_INVALID, "%s: mesh is NULL", fn);
+    nr_ctx *c = m->owner;
+    int rc;
+    if ((rc = grid_check(c, fn, sign, beta, 0)) != NR_OK) return rc;
+    if (source_tri && !vertices) return set_err(c, NR_E_INVALID, "%s: source_tri needs vertices", fn);
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    GridField F{m, sign, 0, beta};
+    const FieldSource field{&F, grid_sparse, grid_label};
+    HIPCHK(c, hipMemsetAsync(m->d_stats, 0, 8, s));
+    SparseDone done;
+    rc = sparse_run(c, nullptr, fn, origin, step, dims, iso, brick, band, vertices, nullptr, source_tri, keys, v_cap, triangles,
+                    t_cap, nv, nt, active_bricks, loc, stats != nullptr, &done, &field);
+    if (rc != NR_OK) return rc;
+    if (stats) {
+        unsigned long long evals = 0;
+        HIPCHK(c, hipMemcpyAsync(&evals, m->d_stats, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        nr_stats st{};
+        st.ray_steps = done.points;
+        st.rays_hit = done.active;
+        st.rays_shaded = (uint64_t)*nv;
+        st.shade_evals = evals;
+        st.launches = done.launches + 1;  // the counter's memset
+        st.ms_total = done.ms;
+        *stats = st;
+    }
+    return NR_OK;
+}
+
+}  // extern "C"
+
 // n caller-supplied rays, or with origins == NULL the W x H pixel rays of the owner's view, through
 // one k_mesh_rays launch; with `out` the payload is the frame (nr_mesh_render).
 static int mesh_rays(nr_trimesh *m, const char *fn, const float *origins, const float *dirs, long n, int W, int H, float tmin,

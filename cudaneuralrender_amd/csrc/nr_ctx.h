@@ -248,13 +248,23 @@ struct SparseDone {
     int launches = 0;
     float ms = 0;
 };
+// A third field for mesh_run and sparse_run, beside c's network and a composed scene: whoever owns
+// it (a triangle mesh: nr_api_trimesh.hip) samples the brick lattices and labels the vertices.  Both
+// enqueue on s and add the kernels they issued to *launches.
+struct FieldSource {
+    void *self;
+    // store == false: the brick-corner values into A.coarse; true: the active bricks' point sets into A.store
+    int (*sample)(void *self, const SparseArgs &A, bool store, hipStream_t s, int *launches);
+    // one int32 per device vertex into d_label (the `part` argument of mesh_run / sparse_run)
+    int (*label)(void *self, const float *d_vertices, int32_t *d_label, size_t nv, hipStream_t s, int *launches);
+};
 int mesh_run(nr_ctx *c, const char *fn, hipStream_t s, const LatticeArgs &L, const float *d_sdf, float iso,
              float *vertices, float *normals, long v_cap, int32_t *triangles, long t_cap, long *nv, long *nt,
-             int loc, int *launches, nr_compose *cp = nullptr, int32_t *part = nullptr);
+             int loc, int *launches, nr_compose *cp = nullptr, int32_t *part = nullptr, const FieldSource *field = nullptr);
 int sparse_run(nr_ctx *c, nr_compose *cp, const char *fn, const float origin[3], const float step[3], const int dims[3],
                float iso, int brick, float band, float *vertices, float *normals, int32_t *part, int64_t *keys,
                long v_cap, int32_t *triangles, long t_cap, long *nv, long *nt, long *active_bricks, int loc, bool timed,
-               SparseDone *done);
+               SparseDone *done, const FieldSource *field = nullptr);
 // The brick samplers of a composed scene (k_compose_sp_coarse; sample: k_compose_sp_sample), one launch on s.
 int compose_sparse_sampler(nr_compose *cp, const SparseArgs &A, bool sample, hipStream_t s);
 // The vertex pass of a composed scene (k_compose_vertex):

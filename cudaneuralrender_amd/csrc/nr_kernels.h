@@ -507,6 +507,15 @@ hipError_t launch_sparse_classify_emit(const SparseArgs &A, hipStream_t st);
 hipError_t launch_sparse_sample(const SparseArgs &A, const MlpArgs &M, int grid, hipStream_t st);
 hipError_t launch_sparse_mesh_count(const SparseArgs &A, hipStream_t st);
 hipError_t launch_sparse_mesh_emit(const SparseArgs &A, hipStream_t st);
+// nr_trimesh_grid.hip: a mesh's signed distance into D.sdf over points generated in the kernel
+// (D.X, D.n, W->X and W->n are not read) -- k_trimesh_grid_distance and, with W (W->sdf = D.sdf), the
+// k_trimesh_grid_winding launch that signs the values in place.  The grid by `cus`, the CU count:
+// 4-wave workgroups, at most 8 per CU.  lattice: D.sdf [L.n], 4 x 4 x 4 blocks per wave; sparse:
+// store == false the brick-corner lattice into D.sdf = S.coarse, store == true the active bricks'
+// point sets into D.sdf = S.store (k_sp_coarse's and k_sp_sample's points and slots).
+hipError_t launch_trimesh_lattice(const TriMeshArgs &D, const TriWindArgs *W, const LatticeArgs &L, int cus, hipStream_t st);
+hipError_t launch_trimesh_sparse(const TriMeshArgs &D, const TriWindArgs *W, const SparseArgs &S, bool store, int cus,
+                                 hipStream_t st);
 hipError_t launch_query(const QueryArgs &Q, const MlpArgs &M, int grid, hipStream_t st);
 hipError_t launch_aa_detect(const AaArgs &X, hipStream_t st);
 hipError_t launch_aa_trace(const RenderArgs &A, const AaArgs &X, const MlpArgs &M, int grid, hipStream_t st);  // 4-wave workgroups

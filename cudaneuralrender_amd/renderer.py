@@ -1570,6 +1570,125 @@ class TriMesh:
                                               NR_DEVICE, ctypes.byref(st) if with_stats else None))
         return st.as_dict() if with_stats else None
 
+    # -- the signed distance on a lattice, remeshed (nr_mesh_sample_grid, nr_mesh_remesh, nr_mesh_remesh_sparse)
+    @staticmethod
+    def _sign(sign):
+        return NR_SAMPLE_SIGN[sign] if isinstance(sign, str) else int(sign)
+
+    def sample_grid(self, origin, step, dims, sign="normal", beta=0.0, brute=False, with_stats=False):
+        """nr_mesh_sample_grid: the mesh's signed distance at the lattice points origin + (i, j, k) *
+        step, dims = (nx, ny, nz), generated in the kernel -- bit for bit distance() (sign "normal") or
+        winding(sdf=True) (sign "winding", with beta) of those points.  Returns float32 [nz, ny, nx]."""
+        o, s, d = _lattice(origin, step, dims)
+        out = np.zeros((d[2], d[1], d[0]), np.float32)
+        st = NRStats()
+        self._chk(self._L.nr_mesh_sample_grid(self._m, _fptr(o), _fptr(s), d, self._sign(sign), float(beta),
+                                                 NR_TRIMESH_BRUTE if brute else 0, out.ctypes.data, NR_HOST,
+                                                 ctypes.byref(st) if with_stats else None))
+        return (out, st.as_dict()) if with_stats else out
+
+    def sample_grid_device(self, sdf_ptr, origin, step, dims, sign="normal", beta=0.0, brute=False, with_stats=False):
+        """nr_mesh_sample_grid into a device buffer of nx * ny * nz float32.  Runs on the renderer's
+        stream and, without stats, returns without waiting."""
+        o, s, d = _lattice(origin, step, dims)
+        st = NRStats()
+        self._chk(self._L.nr_mesh_sample_grid(self._m, _fptr(o), _fptr(s), d, self._sign(sign), float(beta),
+                                                 NR_TRIMESH_BRUTE if brute else 0, ctypes.c_void_p(sdf_ptr), NR_DEVICE,
+                                                 ctypes.byref(st) if with_stats else None))
+        return st.as_dict() if with_stats else None
+
+    def remesh(self, origin, step, dims, iso=0.0, sign="normal", beta=0.0, source_tri=True, with_stats=False):
+        """nr_mesh_remesh: sample the lattice on the device and mesh it, as Renderer.extract_mesh.
+        Returns a dict with "vertices" [nv, 3] float32, "triangles" [nt, 3] int32 and, with
+        source_tri=True, "source_tri" [nv] int32 (the original triangle nearest each vertex).  With sign
+        "winding" an open or self-overlapping mesh comes back closed and consistently oriented.  The
+        count-only call comes first (it samples the lattice too), then the buffers are allocated."""
+        o, s, d = _lattice(origin, step, dims)
+        nv, nt = ctypes.c_long(0), ctypes.c_long(0)
+        st = NRStats()
+
+        def call(V, S, T):
+            return self._L.nr_mesh_remesh(self._m, _fptr(o), _fptr(s), d, float(iso), self._sign(sign), float(beta),
+                                             None if V is None else V.ctypes.data, None if S is None else S.ctypes.data,
+                                             0 if V is None else V.shape[0], None if T is None else T.ctypes.data,
+                                             0 if T is None else T.shape[0], ctypes.byref(nv), ctypes.byref(nt), NR_HOST,
+                                             ctypes.byref(st) if with_stats else None)
+
+        self._chk(call(None, None, None))
+        V, T = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
+        S = np.zeros((nv.value,), np.int32) if source_tri else None
+        if nv.value:
+            self._chk(call(V, S, T))
+        out = {"vertices": V, "triangles": T}
+        if source_tri:
+            out["source_tri"] = S
+        return (out, st.as_dict()) if with_stats else out
+
+    def remesh_device(self, origin, step, dims, vertices_ptr, v_cap, triangles_ptr, t_cap, iso=0.0, sign="normal", beta=0.0,
+                      source_tri_ptr=None, with_stats=False):
+        """nr_mesh_remesh into device buffers (v_cap x 3 float32 vertices, v_cap int32 source_tri, t_cap x
+        3 int32 triangles; both vertices_ptr and triangles_ptr None: count only), on the renderer's
+        stream.  Returns (nv, nt), with the stats dict appended with_stats=True; short capacities raise
+        NRError with nothing written."""
+        o, s, d = _lattice(origin, step, dims)
+        vp = [ctypes.c_void_p(p) if p else None for p in (vertices_ptr, source_tri_ptr, triangles_ptr)]
+        nv, nt = ctypes.c_long(0), ctypes.c_long(0)
+        st = NRStats()
+        self._chk(self._L.nr_mesh_remesh(self._m, _fptr(o), _fptr(s), d, float(iso), self._sign(sign), float(beta), vp[0],
+                                            vp[1], int(v_cap), vp[2], int(t_cap), ctypes.byref(nv), ctypes.byref(nt),
+                                            NR_DEVICE, ctypes.byref(st) if with_stats else None))
+        res = (nv.value, nt.value)
+        return res + (st.as_dict(),) if with_stats else res
+
+    def remesh_sparse(self, origin, step, dims, iso=0.0, sign="normal", beta=0.0, brick=8, band=None, source_tri=True,
+                      keys=True, with_stats=False):
+        """nr_mesh_remesh_sparse: remesh() restricted to the bricks of brick^3 cells that have a corner
+        within `band` of iso (or a sign change, or a NaN), as Renderer.extract_mesh_sparse.  band=None is
+        the brick's diagonal, which is sound for a distance field (brick >= 4); for the winding sign of an
+        open mesh band=float("inf") is the safe choice.  Returns a dict with "vertices", "triangles",
+        "active_bricks" and, as asked, "source_tri" [nv] int32 and "keys" [nv] int64 (np.argsort(keys) is
+        the dense mesh's vertex order)."""
+        o, s, d = _lattice(origin, step, dims)
+        bandf = self.owner._sparse_band(s, brick, band)
+        nv, nt, na = ctypes.c_long(0), ctypes.c_long(0), ctypes.c_long(0)
+        st = NRStats()
+
+        def call(V, S, K, T):
+            return self._L.nr_mesh_remesh_sparse(
+                self._m, _fptr(o), _fptr(s), d, float(iso), self._sign(sign), float(beta), int(brick), bandf,
+                None if V is None else V.ctypes.data, None if S is None else S.ctypes.data,
+                None if K is None else K.ctypes.data, 0 if V is None else V.shape[0],
+                None if T is None else T.ctypes.data, 0 if T is None else T.shape[0],
+                ctypes.byref(nv), ctypes.byref(nt), ctypes.byref(na), NR_HOST, ctypes.byref(st) if with_stats else None)
+
+        self._chk(call(None, None, None, None))
+        V, T = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
+        S = np.zeros((nv.value,), np.int32) if source_tri else None
+        K = np.zeros((nv.value,), np.int64) if keys else None
+        if nv.value:
+            self._chk(call(V, S, K, T))
+        out = {"vertices": V, "triangles": T, "active_bricks": na.value}
+        if source_tri:
+            out["source_tri"] = S
+        if keys:
+            out["keys"] = K
+        return (out, st.as_dict()) if with_stats else out
+
+    def remesh_sparse_device(self, origin, step, dims, vertices_ptr, v_cap, triangles_ptr, t_cap, iso=0.0, sign="normal",
+                             beta=0.0, brick=8, band=None, source_tri_ptr=None, keys_ptr=None, with_stats=False):
+        """nr_mesh_remesh_sparse into device buffers (as remesh_device, and v_cap int64 keys), on the
+        renderer's stream.  Returns (nv, nt, active_bricks), with the stats dict appended with_stats=True."""
+        o, s, d = _lattice(origin, step, dims)
+        vp = [ctypes.c_void_p(p) if p else None for p in (vertices_ptr, source_tri_ptr, keys_ptr, triangles_ptr)]
+        nv, nt, na = ctypes.c_long(0), ctypes.c_long(0), ctypes.c_long(0)
+        st = NRStats()
+        self._chk(self._L.nr_mesh_remesh_sparse(
+            self._m, _fptr(o), _fptr(s), d, float(iso), self._sign(sign), float(beta), int(brick),
+            self.owner._sparse_band(s, brick, band), vp[0], vp[1], vp[2], int(v_cap), vp[3], int(t_cap), ctypes.byref(nv),
+            ctypes.byref(nt), ctypes.byref(na), NR_DEVICE, ctypes.byref(st) if with_stats else None))
+        res = (nv.value, nt.value, na.value)
+        return res + (st.as_dict(),) if with_stats else res
+
     # -- rays (nr_mesh_trace_rays, nr_mesh_gbuffer, nr_mesh_render)
     _RAY_KEYS =("status", "t", "tri", "bary", "position", "normal")
 

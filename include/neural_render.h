@@ -1033,6 +1033,71 @@ int nr_points_order(nr_ctx *ctx, const float *X /*[n][3] or NULL*/, long n, int 
 int nr_mesh_fit_samples(nr_trimesh *m, const nr_sample_opts *opts, float *X /*[n][3]*/, float *Y /*[n]*/, int loc,
                         nr_stats *stats);
 
+/* ---- a mesh's signed distance on a lattice, remeshed ------------------------------- */
+/* (new symbols only: NR_ABI_VERSION stays 3; named nr_mesh_* like every query added since
+ * nr_trimesh_distance -- nr_mesh_winding, nr_mesh_trace_rays, nr_mesh_fit_samples -- the nr_trimesh_*
+ * names being the object's own: create, destroy, info, normals, distance)
+ *
+ * The lattice calls of a triangle mesh: nr_sample_grid, nr_extract_mesh and nr_extract_mesh_sparse
+ * with the mesh's signed distance in place of the network.  The points are generated in the kernel;
+ * there is no new arithmetic, every rule refers to an existing one.  The winding-signed distance of
+ * an open or self-overlapping mesh, remeshed, is a closed and consistently oriented mesh (repair);
+ * iso != 0 gives offset surfaces and shells.
+ *  1. Lattice.  nr_sample_grid's: index (k * ny + j) * nx + i, coordinate origin[a] +
+ *     (float)idx_a * step[a].
+ *  2. Value.  The value at a lattice point is, bit for bit, what the point calls return for X = that
+ *     point's three coordinates: sign = NR_SAMPLE_SIGN_NORMAL nr_trimesh_distance's sdf;
+ *     NR_SAMPLE_SIGN_WINDING nr_mesh_winding's sdf output with that beta (0 = 2.0) -- the distance
+ *     launch's magnitude signed by w >= 0.5f, in a second launch.  NaN results are kept: a
+ *     coordinate that overflows, or a mesh without live triangles.  Both point calls make a point's
+ *     result independent of the other 63 points of its wave, so any assignment of lattice points to
+ *     waves gives these bits; a wave here takes a 4 x 4 x 4 block of the lattice.  NR_TRIMESH_BRUTE
+ *     (nr_mesh_sample_grid's flags) as in the point calls: the same bits without the hierarchy.
+ *  3. nr_mesh_sample_grid: sdf [nz][ny][nx] (loc), dims >= 1, at most 2^30 points.  For
+ *     loc = NR_HOST the lattice is staged in the owner context's buffer.
+ *  4. nr_mesh_remesh = nr_mesh_sample_grid into a buffer the owner context keeps (as
+ *     nr_extract_mesh does), then nr_mesh_grid's passes on it: vertices and triangles are exactly
+ *     nr_mesh_grid's for those values -- order, capacities, the counting call (vertices ==
+ *     triangles == NULL) and errors included; dims >= 2.  source_tri[v], when given, is
+ *     nr_trimesh_distance's tri for vertex v's position, from one more k_trimesh_distance launch
+ *     over the vertex array on the device: the original triangle nearest each new vertex, by which
+ *     a caller carries attributes across.  loc applies to vertices, source_tri and triangles.
+ *  5. nr_mesh_remesh_sparse = rules 1, 2 and 4-9 of nr_extract_mesh_sparse with rule 3's value
+ *     replaced by 2 above and `normals` replaced by source_tri (which needs vertices).
+ *     Why the band is sound here when it is not for a network: the unsigned distance to a mesh is
+ *     1-Lipschitz, and so is the signed one across a closed surface.  A brick that holds a crossing
+ *     cell has, on a crossing edge of that cell, a point at the level; that point is within half
+ *     the brick's diagonal plus one cell diagonal of the brick's nearest corner, so that corner's
+ *     value is within that much of iso -- at most the brick's diagonal for B >= 4 (B/2 + 1 <= B
+ *     cells per axis), which is the band the Python wrapper passes for band=None.
+ *     What stays unproven: the f32 rounding of the distances (a few ulp against a band of whole
+ *     cells); the sign from the beta-approximated winding number; and the winding sign's jumps away
+ *     from the surface of an open mesh -- the cap that closes a hole is a level crossing with
+ *     |sdf| large on both sides, and it can pass through a brick without flipping one of its
+ *     corners.  There band = +INFINITY is the safe choice.
+ *  6. Stats (may be NULL).  ray_steps = lattice points evaluated (sparse: rule 7 of
+ *     nr_extract_mesh_sparse); shade_evals = point-triangle evaluations (source_tri's launch
+ *     included) plus, with NR_SAMPLE_SIGN_WINDING, the solid angles and expansions; rays_hit =
+ *     active bricks (sparse); rays_shaded = *nv (the two remesh calls); launches and ms_total as
+ *     elsewhere.
+ *  7. Errors.  The lattice and capacity errors are those of nr_sample_grid, nr_extract_mesh and
+ *     nr_extract_mesh_sparse (no NR_E_STATE / NR_E_FORMAT: no network is needed).  NR_E_INVALID
+ *     too for an unknown sign, a beta that is negative or not finite, unknown flag bits, and a
+ *     NULL mesh (recorded without a context).
+ *  8. Scratch.  The owner context's, shared with its own lattice calls: do not run them
+ *     concurrently. */
+int nr_mesh_sample_grid(nr_trimesh *m, const float origin[3], const float step[3], const int dims[3],
+                           int sign, float beta /*WINDING only; 0 = 2.0*/, int flags /*0 or NR_TRIMESH_BRUTE*/,
+                           float *sdf /*[nz][ny][nx]*/, int loc, nr_stats *stats);
+int nr_mesh_remesh(nr_trimesh *m, const float origin[3], const float step[3], const int dims[3], float iso,
+                      int sign, float beta, float *vertices /*[v_cap][3]*/, int32_t *source_tri /*[v_cap] or NULL*/,
+                      long v_cap, int32_t *triangles /*[t_cap][3]*/, long t_cap, long *nv, long *nt, int loc,
+                      nr_stats *stats);
+int nr_mesh_remesh_sparse(nr_trimesh *m, const float origin[3], const float step[3], const int dims[3], float iso,
+                             int sign, float beta, int brick, float band, float *vertices, int32_t *source_tri,
+                             int64_t *keys /*or NULL*/, long v_cap, int32_t *triangles, long t_cap, long *nv, long *nt,
+                             long *active_bricks /*or NULL*/, int loc, nr_stats *stats);
+
 /* ---- composed scenes: several networks, placed and combined by CSG ---------------- */
 /* (new symbols and new structs only: NR_ABI_VERSION stays 3, nr_stats is unchanged)
  *

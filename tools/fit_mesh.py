@@ -13,6 +13,8 @@ of a closed one.  A [3, 32 x 4, 1]
 student, batch 2^16, lr 1e-3, --epochs epochs; then load_into a renderer and a 256^2 frame, whose
 silhouette is compared with the mesh's own (TriMesh.gbuffer through the same camera) and, when the
 mesh came from a network, with that network's.
+--volume-iou N adds a camera-free metric: the IoU of {student < 0} (Renderer.sample_grid, scene tanh) and
+{mesh sdf < 0} (TriMesh.sample_grid with the fit's sign) on an N^3 lattice over the box [-1.3, 1.3]^3.
 --sampler device replaces the torch recipe by one nr_mesh_fit_samples call: half the points on the surface in
 proportion to triangle area at sigma 0.03, half uniform in the box [-1.3, 1.3]^3.
 Runs on the GPU box: python3 tools/fit_mesh.py [mesh.obj]"""
@@ -40,6 +42,8 @@ def main():
     ap.add_argument("--sign", choices=("normal", "winding"), help="default: normal for a closed mesh, winding otherwise")
     ap.add_argument("--sampler", choices=("torch", "device"), default="torch",
                     help="torch: the recipe above (the recorded numbers); device: one nr_mesh_fit_samples call")
+    ap.add_argument("--volume-iou", type=int, default=0, metavar="N",
+                    help="also the IoU of {student < 0} and {mesh sdf < 0} on an N^3 lattice over [-1.3, 1.3]^3")
     ap.add_argument("--drop-x", type=float, nargs=2, metavar=("LO", "HI"), help="remove the triangles whose centroid has LO <= x <= HI")
     args = ap.parse_args()
     n = args.points
@@ -85,6 +89,15 @@ def main():
         sm = gb["status"] == 2  # NR_RAY_HIT
         print(f"mesh at 256^2: {int(sm.sum())} px in {gst['ms_total']:.2f} ms ({gst['shade_evals'] / sm.size:.1f} ray-triangle "
               f"evaluations per pixel)")
+        mesh_in = None
+        if args.volume_iou >= 2:
+            N = args.volume_iou
+            vstep = np.float32(2.6) / np.float32(N - 1)
+            lattice = ((-1.3, -1.3, -1.3), (vstep, vstep, vstep), (N, N, N))
+            vals, vst = m.sample_grid(*lattice, sign=sign, with_stats=True)
+            mesh_in = vals < 0
+            print(f"mesh on the {N}^3 lattice over [-1.3, 1.3]^3 (sign: {sign}): {int(mesh_in.sum())} points inside, "
+                  f"{vst['ms_total']:.2f} ms, {vst['shade_evals'] / vals.size:.1f} evaluations per point")
         if args.sampler == "device":
             # half on the surface in proportion to area, jittered by 0.03, half uniform in the box: drawn, ordered,
             # labelled and shuffled by the library, left on the device
@@ -155,6 +168,10 @@ def main():
     sz = student.render(256, 256, 256)[0] != 0
     print(f"silhouette at 256^2, scene tanh: mesh {int(sm.sum())} px, student fitted to it {int(sz.sum())} px, IoU against the mesh "
           f"{iou(sm, sz):.4f}")
+    if mesh_in is not None:
+        net_in = student.sample_grid(*lattice) < 0
+        print(f"volume at {args.volume_iou}^3 over [-1.3, 1.3]^3, scene tanh: mesh {int(mesh_in.sum())} points inside, student "
+              f"{int(net_in.sum())}, IoU {iou(mesh_in, net_in):.4f}")
     if source is not None:
         st = silhouette(source)
         print(f"silhouette at 256^2, scene v1: source network {int(st.sum())} px, student fitted to its mesh {int(ss.sum())} px, "
