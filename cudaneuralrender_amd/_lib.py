@@ -55,6 +55,7 @@ EXPORTS = [
     "nr_mesh_trace_rays", "nr_mesh_gbuffer", "nr_mesh_render",
     "nr_mesh_area_table", "nr_mesh_sample", "nr_points_order", "nr_mesh_fit_samples",
     "nr_mesh_sample_grid", "nr_mesh_remesh", "nr_mesh_remesh_sparse",
+    "nr_mesh_create_device", "nr_mesh_download",
 ]
 # nr_trimesh_distance: flags, and the feature codes of its `feature` output
 NR_TRIMESH_BRUTE = 1
@@ -340,6 +341,8 @@ def lib():
                                   ctypes.POINTER(NRStats)]),
         "nr_mesh_remesh_sparse": (I, [P, FP, FP, IP, F, I, F, I, F, P, P, P, L64, P, L64, ctypes.POINTER(L64),
                                          ctypes.POINTER(L64), ctypes.POINTER(L64), I, ctypes.POINTER(NRStats)]),
+        "nr_mesh_create_device": (I, [P, P, L64, P, L64, I, ctypes.POINTER(P), ctypes.POINTER(NRStats)]),
+        "nr_mesh_download": (I, [P, P, P, P, P, P, ctypes.POINTER(L64), ctypes.POINTER(L64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

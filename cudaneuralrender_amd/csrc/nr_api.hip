@@ -327,7 +327,7 @@ int nr_destroy(nr_ctx *c) {
     dfree(c->d_ls); dfree(c->d_lgbuf); dfree(c->d_lao);
     dfree(c->d_ps);
     dfree(c->d_grid); dfree(c->d_mesh); dfree(c->d_mio); dfree(c->d_spb); dfree(c->d_spa);
-    dfree(c->d_sort); dfree(c->d_sortio); dfree(c->d_fitsamp);
+    dfree(c->d_sort); dfree(c->d_sortio); dfree(c->d_fitsamp); dfree(c->d_tbuild);
     if (c->h_frames) (void)hipHostFree(c->h_frames);
     if (c->ev_frames) (void)hipEventDestroy(c->ev_frames);
     if (c->h_ctr) (void)hipHostFree(c->h_ctr);

@@ -1,6 +1,7 @@
 // nr_api_trimesh.hip -- the C ABI's triangle meshes (nr_trimesh_*).
 #include <climits>
 #include <cmath>
+#include <map>
 #include <new>
 #include <vector>
 
@@ -9,8 +10,9 @@
 using namespace nr;
 
 // ---- triangle meshes (nr_trimesh_*; nr_trimesh_host.cpp, nr_trimesh.hip, nr_winding.hip, nr_mesh_rays.hip) ----
-// The hierarchy with its moments, the reordered triangles and the pseudonormal table are built on
-// the host at create time and live on the device; a distance query is one launch, a winding query
+// The hierarchy with its moments, the reordered triangles and the pseudonormal table are built at
+// create time, on the host (nr_trimesh_create) or by kernels (nr_mesh_create_device, further
+// down), and live on the device; a distance query is one launch, a winding query
 // one, or two with the sdf output, a ray query (nr_mesh_rays.hip) one.  (struct nr_trimesh: nr_ctx.h)
 
 extern "C" {
@@ -187,6 +189,236 @@ int nr_mesh_winding(nr_trimesh *m, const float *X, long n, float beta, float *wi
     st.shade_evals = evals;
     st.launches = A.sdf ? 3 : 2;  // the counter's memset, k_trimesh_distance for sdf, k_trimesh_winding
     *stats = st;
+    return NR_OK;
+}
+
+}  // extern "C"
+
+// ---- the device build (nr_trimesh_build.hip) and the download of what a mesh holds ----
+// The kernels do everything but the tree's shape, which depends on (ntl, leaf) alone: made here
+// once ntl is known (the first of the two records read back) and uploaded.
+
+namespace {
+
+// the float behind an ordered integer of TriBuildHead
+float tb_decode(uint32_t e) {
+    const uint32_t b = (e & 0x80000000u) ? e ^ 0x80000000u : ~e;
+    float f;
+    memcpy(&f, &b, 4);
+    return f;
+}
+
+// the nodes of Builder::build's tree over n positions (nr_trimesh_host.cpp): non-decreasing in n
+long tree_nodes(long n, int leaf, std::map<long, long> &memo) {
+    if (n <= leaf) return 1;
+    const auto it = memo.find(n);
+    if (it != memo.end()) return it->second;
+    const long half = (n + 1) / 2;
+    return memo[n] = 1 + tree_nodes(half, leaf, memo) + tree_nodes(n - half, leaf, memo);
+}
+
+// That tree's shape in preorder: links, position ranges, and `list` = the leaves, then the inner nodes
+// level by level from the deepest (level_off: where each of those levels starts).
+struct TreeShape {
+    std::vector<int32_t> w3, w7, first, count, list;
+    std::vector<int> level_off;
+    int nleaves = 0, depth = 0;
+};
+void tree_shape(long ntl, int leaf, TreeShape &S) {
+    struct Todo { int32_t first, count, parent; int level; bool right; };
+    std::vector<Todo> todo{{0, (int32_t)ntl, -1, 1, false}};
+    std::vector<int> level;
+    while (!todo.empty()) {
+        const Todo t = todo.back();
+        todo.pop_back();
+        const int32_t me = (int32_t)S.w3.size();
+        if (t.parent >= 0) (t.right ? S.w7 : S.w3)[(size_t)t.parent] = me;
+        S.first.push_back(t.first);
+        S.count.push_back(t.count);
+        level.push_back(t.level);
+        S.depth = std::max(S.depth, t.level);
+        if (t.count <= leaf) {
+            S.w3.push_back(t.first);
+            S.w7.push_back(-t.count);
+            continue;
+        }
+        S.w3.push_back(0);
+        S.w7.push_back(0);
+        const int32_t half = (t.count + 1) / 2;
+        todo.push_back({t.first + half, t.count - half, me, t.level + 1, true});
+        todo.push_back({t.first, half, me, t.level + 1, false});  // (the left child is numbered first)
+    }
+    const size_t nn = S.w3.size();
+    S.list.reserve(nn);
+    for (size_t i = 0; i < nn; ++i)
+        if (S.w7[i] <= 0) S.list.push_back((int32_t)i);
+    S.nleaves = (int)S.list.size();
+    // the inner nodes by level, deepest first (level depth holds leaves only)
+    std::vector<int> at((size_t)S.depth + 1, 0);  // at[l]: the inner nodes of levels deeper than l, then the cursor of level l
+    for (size_t i = 0; i < nn; ++i)
+        if (S.w7[i] > 0) ++at[(size_t)level[i] - 1];
+    for (int l = S.depth - 1; l >= 0; --l) at[(size_t)l] += at[(size_t)l + 1];
+    S.level_off.push_back(0);
+    for (int l = S.depth - 1; l >= 1; --l) S.level_off.push_back(at[(size_t)l - 1]);
+    S.list.resize(nn);
+    for (size_t i = 0; i < nn; ++i)
+        if (S.w7[i] > 0) S.list[(size_t)S.nleaves + (size_t)at[(size_t)level[i]]++] = (int32_t)i;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nr_mesh_create_device(nr_ctx *owner, const float *d_vertices, long nv, const int32_t *d_triangles, long nt, int leaf,
+                             nr_trimesh **out, nr_stats *stats) {
+    const char *fn = "nr_mesh_create_device";
+    if (out) *out = nullptr;
+    if (!owner || !d_vertices || !d_triangles || !out) return set_err(owner, NR_E_INVALID, "%s: NULL argument", fn);
+    if (nv < 1 || nv > (long)INT32_MAX) return set_err(owner, NR_E_INVALID, "%s: nv = %ld outside [1, 2^31)", fn, nv);
+    if (nt < 1 || nt > (1l << 24)) return set_err(owner, NR_E_INVALID, "%s: nt = %ld outside [1, 2^24]", fn, nt);
+    if (leaf < 0 || leaf > 32) return set_err(owner, NR_E_INVALID, "%s: leaf = %d outside 0..32", fn, leaf);
+    if (leaf == 0) leaf = TRIMESH_LEAF_DEFAULT;
+    nr_ctx *c = owner;
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    // scratch: the two sorts in d_sort; in d_tbuild (8-byte words) the record, fn, the areas and their
+    // block sums, and per node of the largest tree nt triangles can give the shape, sums, box and r2
+    const size_t NT = (size_t)nt, N3 = 3 * NT;
+    const size_t tri_words = sort_scratch_words(NT), nblk_a = (NT + 255) / 256;
+    std::map<long, long> memo;
+    const size_t nn_max = (size_t)tree_nodes(nt, leaf, memo);
+    const size_t w_head = 16, w_fn = 3 * NT, w_area = NT, w_base = nblk_a + 1, w_shape = (5 * nn_max + 1) / 2;
+    const size_t w_sums = 19 * nn_max, w_box = 3 * nn_max, w_r2 = nn_max;
+    int rc;
+    if ((rc = ensure_buf(c, c->d_sort, c->cap_sort, tri_words + sort_scratch_words(N3))) != NR_OK) return rc;
+    if ((rc = ensure_buf(c, c->d_tbuild, c->cap_tbuild, w_head + w_fn + w_area + w_base + w_shape + w_sums + w_box + w_r2)) != NR_OK)
+        return rc;
+    nr_trimesh *m = new (std::nothrow) nr_trimesh();
+    if (!m) return set_err(c, NR_E_NOMEM, "out of host memory");
+    m->owner = c;
+    m->nv = nv; m->nt = nt;
+    // from here on every exit but the last frees m and what it holds
+    auto fail = [&](int code, hipError_t e) {
+        (void)hipStreamSynchronize(s);
+        dfree(m->d_nodes); dfree(m->d_tris); dfree(m->d_table); dfree(m->d_moments); dfree(m->d_area); dfree(m->d_stats);
+        delete m;
+        if (e != hipSuccess) return set_err(c, e == hipErrorOutOfMemory ? NR_E_NOMEM : NR_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+        return code;
+    };
+    TriBuildArgs A{};
+    A.V = d_vertices; A.T = d_triangles; A.nv = nv; A.nt = nt;
+    {
+        uint32_t *w = c->d_sort;
+        A.tkeys[0] = w; A.tvals[0] = w + NT; A.tkeys[1] = w + 2 * NT; A.tvals[1] = w + 3 * NT; A.ttable = w + 4 * NT;
+        w += tri_words;
+        A.ckeys[0] = w; A.cvals[0] = w + N3; A.ckeys[1] = w + 2 * N3; A.cvals[1] = w + 3 * N3; A.ctable = w + 4 * N3;
+        unsigned long long *q = c->d_tbuild;
+        A.head = reinterpret_cast<TriBuildHead *>(q); q += w_head;
+        A.fn = reinterpret_cast<double *>(q); q += w_fn;
+        A.area = reinterpret_cast<double *>(q); q += w_area;
+        A.base = reinterpret_cast<double *>(q); q += w_base;
+        int32_t *shape = reinterpret_cast<int32_t *>(q); q += w_shape;
+        A.w3 = shape; A.w7 = shape + nn_max; A.first = shape + 2 * nn_max; A.count = shape + 3 * nn_max; A.list = shape + 4 * nn_max;
+        A.sums = reinterpret_cast<double *>(q); q += w_sums;
+        A.box = reinterpret_cast<float *>(q); q += w_box;
+        A.r2 = q;
+    }
+    hipError_t e = hipMalloc(&m->d_table, NT * 21 * 4);
+    if (e == hipSuccess) e = hipMalloc(&m->d_stats, 128);
+    if (e != hipSuccess) return fail(0, e);
+    A.table = m->d_table;
+    int launches = TRIBUILD_SCAN_LAUNCHES;
+    TriBuildHead head;
+    e = hipEventRecord(c->ev0, s);
+    if (e == hipSuccess) e = launch_tribuild_scan(A, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&head, A.head, sizeof head, hipMemcpyDeviceToHost, s);  // the first record
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(0, e);
+    if (head.err & 1u) return fail(set_err(c, NR_E_INVALID, "%s: a vertex index outside 0..%ld", fn, nv - 1), hipSuccess);
+    if (head.err & 2u) return fail(set_err(c, NR_E_INVALID, "%s: a vertex that is not finite", fn), hipSuccess);
+    // the bound and the boxes' slack, as trimesh_build forms them
+    double extent = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        m->lo[a] = tb_decode(head.lo[a]);
+        m->hi[a] = tb_decode(head.hi[a]);
+        extent = std::max(extent, (double)m->hi[a] - (double)m->lo[a]);
+    }
+    float maxabs;
+    memcpy(&maxabs, &head.maxabs, 4);
+    A.slack = std::ldexp((double)maxabs + extent, -TRIMESH_SLACK_SHIFT);
+    m->scale = std::ldexp((float)A.slack, TRIMESH_SLACK_SHIFT);
+    const long ntl = (long)head.ntl;
+    TreeShape S;
+    tree_shape(ntl, leaf, S);
+    const size_t nn = S.w3.size();
+    m->ntl = ntl; m->nnodes = (long)nn; m->depth = S.depth;
+    const size_t ntl1 = (size_t)std::max(ntl, 1l);
+    e = hipMalloc(&m->d_nodes, nn * 8 * 4);
+    if (e == hipSuccess) e = hipMalloc(&m->d_moments, nn * 16 * 4);
+    if (e == hipSuccess) e = hipMalloc(&m->d_tris, ntl1 * 12 * 4);
+    if (e == hipSuccess) e = hipMalloc(&m->d_area, ntl1 * 4);
+    if (e == hipSuccess) e = launch_tribuild_table(A, s);
+    launches += TRIBUILD_TABLE_LAUNCHES;
+    if (e != hipSuccess) return fail(0, e);
+    float empty[8];  // ntl = 0: the one empty leaf trimesh_build makes
+    if (ntl > 0) {
+        const int32_t *parts[5] = {S.w3.data(), S.w7.data(), S.first.data(), S.count.data(), S.list.data()};
+        const int32_t *dst[5] = {A.w3, A.w7, A.first, A.count, A.list};
+        for (int k = 0; k < 5 && e == hipSuccess; ++k)
+            e = hipMemcpyAsync(const_cast<int32_t *>(dst[k]), parts[k], nn * 4, hipMemcpyHostToDevice, s);
+        A.ntl = (int)ntl; A.nnodes = (int)nn; A.nleaves = S.nleaves; A.depth = S.depth;
+        A.level_off = S.level_off.data();
+        A.ninner_levels = (int)S.level_off.size() - 1;
+        A.nodes = m->d_nodes; A.tris = m->d_tris; A.moments = m->d_moments; A.thresholds = m->d_area;
+        if (e == hipSuccess) e = launch_tribuild_tree(A, s);
+        launches += tribuild_tree_launches(A);
+    } else {
+        for (int a = 0; a < 3; ++a) { empty[a] = INFINITY; empty[4 + a] = -INFINITY; }
+        empty[3] = 0.0f; empty[7] = 0.0f;
+        e = hipMemcpyAsync(m->d_nodes, empty, sizeof empty, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemsetAsync(m->d_moments, 0, 16 * 4, s);
+        if (e == hipSuccess) e = hipMemsetAsync(m->d_tris, 0, 12 * 4, s);
+        if (e == hipSuccess) e = hipMemsetAsync(m->d_area, 0, 4, s);
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&head, A.head, sizeof head, hipMemcpyDeviceToHost, s);  // the second record
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(0, e);
+    m->closed = head.open ? 0 : 1;
+    m->area_last = head.area_last;
+    if (stats) {
+        nr_stats st{};
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        st.ray_steps = (uint64_t)nt;
+        st.launches = launches;
+        st.ms_total = ms;
+        *stats = st;
+    }
+    *out = m;
+    return NR_OK;
+}
+
+int nr_mesh_download(nr_trimesh *m, float *nodes, int32_t *order, float *moments, float *table, uint32_t *thresholds, long *ntl,
+                        long *area_last) {
+    if (!m) return set_err(nullptr, NR_E_INVALID, "nr_mesh_download: mesh is NULL");
+    nr_ctx *c = m->owner;
+    if (ntl) *ntl = m->ntl;
+    if (area_last) *area_last = m->area_last;
+    HIPCHK(c, hipSetDevice(c->device));
+    GET_STREAM(c, s);
+    const size_t nn = (size_t)m->nnodes, n = (size_t)m->ntl;
+    if (nodes) HIPCHK(c, hipMemcpyAsync(nodes, m->d_nodes, nn * 8 * 4, hipMemcpyDeviceToHost, s));
+    if (moments) HIPCHK(c, hipMemcpyAsync(moments, m->d_moments, nn * 16 * 4, hipMemcpyDeviceToHost, s));
+    if (table) HIPCHK(c, hipMemcpyAsync(table, m->d_table, (size_t)m->nt * 21 * 4, hipMemcpyDeviceToHost, s));
+    if (thresholds && n) HIPCHK(c, hipMemcpyAsync(thresholds, m->d_area, n * 4, hipMemcpyDeviceToHost, s));
+    std::vector<float> tris;
+    if (order && n) {
+        tris.resize(n * 12);
+        HIPCHK(c, hipMemcpyAsync(tris.data(), m->d_tris, n * 12 * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (size_t p = 0; p < tris.size() / 12; ++p) memcpy(order + p, &tris[p * 12 + 3], 4);  // word 3 of every position's 12
     return NR_OK;
 }
 

@@ -122,6 +122,10 @@ struct nr_ctx {
     size_t cap_sortio = 0;
     float *d_fitsamp = nullptr;
     size_t cap_fitsamp = 0;
+    // nr_mesh_create_device: its two sorts take d_sort; the read-back record, the f64 face normals
+    // and areas, the tree's shape and the nodes' raw sums (8-byte words), reused across calls
+    unsigned long long *d_tbuild = nullptr;
+    size_t cap_tbuild = 0;
 
     // settings
     float inv_view[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 2};
@@ -166,7 +170,7 @@ struct nr_compose;
 
 // A triangle mesh on the device (nr_api_trimesh.hip creates and queries it, nr_api_sample.hip samples
 // it): the hierarchy with its moments, the reordered triangles, the pseudonormal table and the area
-// table, all built on the host at create time.
+// table, all built on the host at create time (nr_trimesh_create) or by kernels (nr_mesh_create_device).
 struct nr_trimesh {
     nr_ctx *owner = nullptr;
     long nv = 0, nt = 0, nnodes = 0, ntl = 0;

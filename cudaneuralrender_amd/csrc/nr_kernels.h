@@ -394,9 +394,61 @@ struct SortArgs {
 inline size_t sort_scratch_words(size_t n) { return 4 * n + 256 * ((n + SORT_TILE - 1) / SORT_TILE); }
 hipError_t launch_points_order(const SortArgs &A, hipStream_t st);  // 13 launches
 constexpr int SORT_LAUNCHES = 13;
+// The four passes alone, for any n 32-bit keys with a 32-bit payload already in (keys[0], vals[0]):
+// the sorted keys end in keys[0], the payloads in vals_out, or in vals[0] where vals_out is NULL
+// (nr_trimesh_build.hip sorts triangles and corners with it).  12 launches.
+hipError_t launch_sort_pairs(uint32_t *const keys[2], uint32_t *const vals[2], long n, uint32_t *table, int nblk,
+                             uint32_t *vals_out, hipStream_t st);
+constexpr int SORT_PAIR_LAUNCHES = 12;
 // dst[j] = src[perm[j]] of float3 rows, and col_dst[j] = col_src[perm[j]] where col_dst is not NULL
 hipError_t launch_gather(const float *src, const float *col_src, const int32_t *perm, long n, float *dst, float *col_dst,
                          hipStream_t st);
+
+// The device build of a nr_trimesh (nr_trimesh_build.hip; nr_mesh_create_device): the table, the
+// order, the tree with its moments and the area table from vertices and triangles in device memory,
+// by the contract of a device-built mesh in include/neural_render.h.  TriBuildHead is the only thing
+// the host reads back: once after launch_tribuild_scan (err, the bound, ntl), once at the end.
+struct TriBuildHead {             // 128 bytes
+    uint32_t lo[3], hi[3];        // the vertices' bound, each float as an ordered integer: a negative
+                                  // float's bits inverted, any other's with the top bit set (-0 < +0)
+    uint32_t maxabs;              // the bits of the largest |coordinate|
+    uint32_t err;                 // bit 0: an index outside 0..nv-1; bit 1: a vertex that is not finite
+    uint32_t ntl;                 // the live triangles
+    uint32_t open;                // != 0: some edge is not used exactly twice, once each way
+    int32_t area_last;            // L of the area table
+    uint32_t pad[21];
+};
+struct TriBuildArgs {
+    const float *V;               // [nv][3]
+    const int32_t *T;             // [nt][3]
+    long nv, nt;
+    TriBuildHead *head;
+    uint32_t *tkeys[2], *tvals[2], *ttable;  // the triangle sort: [nt] each, the digit table; order = tvals[0]
+    uint32_t *ckeys[2], *cvals[2], *ctable;  // the corner sort: [3 nt] each; after it [1] hold rank and group head
+    double *fn;                   // [nt][3] the f64 face normals
+    float *table;                 // [nt][7][3]
+    // from here on: set after the first read-back
+    double slack;
+    int ntl, nnodes, nleaves, depth;
+    const int32_t *w3, *w7, *first, *count;  // [nnodes] the tree's shape (host-made)
+    const int32_t *list;          // [nnodes] the leaves, then the inner nodes level by level, deepest first
+    const int *level_off;         // host: [ninner_levels + 1] offsets into list after the leaves
+    int ninner_levels;
+    double *sums;                 // [nnodes][19] sa, sx, mx, N, P
+    float *box;                   // [nnodes][6] the exact bound of the node's corners
+    unsigned long long *r2;       // [nnodes] the bits of the largest squared corner distance
+    double *area;                 // [ntl] |A_p|, then the running sum inside each block of 256
+    double *base;                 // [ceil(ntl / 256) + 1] block totals, then their exclusive sums and the total
+    float *nodes, *tris, *moments;  // the mesh's arrays
+    uint32_t *thresholds;
+};
+hipError_t launch_tribuild_scan(const TriBuildArgs &A, hipStream_t st);   // the head's start values, the bound, faces and keys
+constexpr int TRIBUILD_SCAN_LAUNCHES = 3;
+hipError_t launch_tribuild_table(const TriBuildArgs &A, hipStream_t st);  // both sorts, vertex and edge sums
+constexpr int TRIBUILD_TABLE_LAUNCHES = 2 * SORT_PAIR_LAUNCHES + 2;
+// the gather, the leaves, one launch per level of inner nodes, the finish, R2 (two) and the area table (three)
+hipError_t launch_tribuild_tree(const TriBuildArgs &A, hipStream_t st);
+inline int tribuild_tree_launches(const TriBuildArgs &A) { return 8 + A.ninner_levels; }
 
 // Composed scenes (nr_compose.hip; nr_compose_*): the distinct fp32 packs back to back in one device
 // buffer (staged into dynamic LDS in that order), the parts, and the queried rays or points.  The

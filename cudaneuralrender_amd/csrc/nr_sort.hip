@@ -204,17 +204,22 @@ int stride_grid(long n) { return (int)std::max<long>(1, std::min<long>((n + 255)
 
 }  // namespace
 
-hipError_t launch_points_order(const SortArgs &A, hipStream_t st) {
-    hipLaunchKernelGGL(k_sort_keys, dim3(stride_grid(A.n)), dim3(256), 0, st, A);
+hipError_t launch_sort_pairs(uint32_t *const keys[2], uint32_t *const vals[2], long n, uint32_t *table, int nblk,
+                             uint32_t *vals_out, hipStream_t st) {
     for (int pass = 0; pass < 4; ++pass) {
         const int in = pass & 1, out = in ^ 1;
         const int shift = 8 * pass;
-        hipLaunchKernelGGL(k_sort_hist, dim3(A.nblk), dim3(256), 0, st, A.keys[in], A.n, shift, A.table, A.nblk);
-        hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(1024), 0, st, A.table, 256 * A.nblk);
-        hipLaunchKernelGGL(k_sort_scatter, dim3(A.nblk), dim3(256), 0, st, A.keys[in], A.vals[in], A.n, shift, A.table, A.nblk,
-                           A.keys[out], pass == 3 ? reinterpret_cast<uint32_t *>(A.perm) : A.vals[out]);
+        hipLaunchKernelGGL(k_sort_hist, dim3(nblk), dim3(256), 0, st, keys[in], n, shift, table, nblk);
+        hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(1024), 0, st, table, 256 * nblk);
+        hipLaunchKernelGGL(k_sort_scatter, dim3(nblk), dim3(256), 0, st, keys[in], vals[in], n, shift, table, nblk, keys[out],
+                           pass == 3 && vals_out ? vals_out : vals[out]);
     }
     return hipGetLastError();
+}
+
+hipError_t launch_points_order(const SortArgs &A, hipStream_t st) {
+    hipLaunchKernelGGL(k_sort_keys, dim3(stride_grid(A.n)), dim3(256), 0, st, A);
+    return launch_sort_pairs(A.keys, A.vals, A.n, A.table, A.nblk, reinterpret_cast<uint32_t *>(A.perm), st);
 }
 
 hipError_t launch_gather(const float *src, const float *col_src, const int32_t *perm, long n, float *dst, float *col_dst,

@@ -1416,15 +1416,64 @@ class TriMesh:
     """nr_trimesh: a triangle mesh, its pseudonormals and a box hierarchy on the device, queried for the
     signed distance of points -- bit for bit the arithmetic written in include/neural_render.h.
     `renderer` supplies the device and the stream (it needs no network).  leaf: triangles per leaf of
-    the hierarchy, 0 = 8.  Close the mesh before its renderer."""
+    the hierarchy, 0 = 8.  build: "host" (nr_trimesh_create: the spatial-median tree, built on one host
+    thread) or "device" (the arrays are uploaded and nr_mesh_create_device builds the Morton-ordered
+    tree with kernels; from_device takes arrays that are on the device already).  Close the mesh before
+    its renderer."""
 
-    def __init__(self, renderer, vertices, triangles, leaf=0):
+    def __init__(self, renderer, vertices, triangles, leaf=0, build="host"):
         self._L = lib()
         self.owner = renderer
         self._m = ctypes.c_void_p()
+        self.build_stats = None
         V, T = _mesh_arrays(vertices, triangles)
-        renderer._chk(self._L.nr_trimesh_create(renderer._ctx, V.ctypes.data, V.shape[0], T.ctypes.data, T.shape[0],
-                                                int(leaf), ctypes.byref(self._m)))
+        if build == "host":
+            renderer._chk(self._L.nr_trimesh_create(renderer._ctx, V.ctypes.data, V.shape[0], T.ctypes.data, T.shape[0],
+                                                    int(leaf), ctypes.byref(self._m)))
+        elif build == "device":
+            import torch
+            dev = torch.device("cuda", renderer.device)
+            dV, dT = torch.from_numpy(V.copy()).to(dev), torch.from_numpy(T.copy()).to(dev)
+            torch.cuda.synchronize(dev)
+            self._create_device(dV.data_ptr(), V.shape[0], dT.data_ptr(), T.shape[0], leaf, False)
+        else:
+            raise ValueError(f"build must be 'host' or 'device', got {build!r}")
+
+    def _create_device(self, vertices_ptr, nv, triangles_ptr, nt, leaf, with_stats):
+        st = NRStats()
+        self.owner._chk(self._L.nr_mesh_create_device(self.owner._ctx, ctypes.c_void_p(vertices_ptr), int(nv),
+                                                         ctypes.c_void_p(triangles_ptr), int(nt), int(leaf),
+                                                         ctypes.byref(self._m), ctypes.byref(st) if with_stats else None))
+        self.build_stats = st.as_dict() if with_stats else None
+
+    @classmethod
+    def from_device(cls, renderer, vertices_ptr, nv, triangles_ptr, nt, leaf=0, with_stats=False):
+        """nr_mesh_create_device on device buffers (float32 vertices [nv, 3], int32 triangles [nt, 3]),
+        e.g. extract_mesh_device's: the mesh is built by kernels and nothing but two small records
+        crosses to the host.  The buffers are read during the call only.  With with_stats the build's
+        statistics are left in .build_stats."""
+        self = cls.__new__(cls)
+        self._L = lib()
+        self.owner = renderer
+        self._m = ctypes.c_void_p()
+        self._create_device(vertices_ptr, nv, triangles_ptr, nt, leaf, with_stats)
+        return self
+
+    def download(self):
+        """nr_mesh_download: {"nodes" [nnodes, 8], "order" [ntl] int32, "moments" [nnodes, 16], "table"
+        [nt, 7, 3], "thresholds" [ntl] uint32, "ntl", "area_last"} -- what the object holds on the device,
+        however it was built (words 3 and 7 of a node are int32, as trimesh_hierarchy's)."""
+        info = self.info()
+        ntl, last = ctypes.c_long(0), ctypes.c_long(0)
+        self._chk(self._L.nr_mesh_download(self._m, None, None, None, None, None, ctypes.byref(ntl), ctypes.byref(last)))
+        out = {"nodes": np.zeros((info["nodes"], 8), np.float32), "order": np.zeros(ntl.value, np.int32),
+               "moments": np.zeros((info["nodes"], 16), np.float32), "table": np.zeros((info["nt"], 7, 3), np.float32),
+               "thresholds": np.zeros(ntl.value, np.uint32)}
+        self._chk(self._L.nr_mesh_download(self._m, *[out[k].ctypes.data if out[k].size else None
+                                                         for k in ("nodes", "order", "moments", "table", "thresholds")],
+                                              None, None))
+        out["ntl"], out["area_last"] = ntl.value, last.value
+        return out
 
     def close(self):
         if self._m:

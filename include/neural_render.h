@@ -1098,6 +1098,71 @@ int nr_mesh_remesh_sparse(nr_trimesh *m, const float origin[3], const float step
                              int64_t *keys /*or NULL*/, long v_cap, int32_t *triangles, long t_cap, long *nv, long *nt,
                              long *active_bricks /*or NULL*/, int loc, nr_stats *stats);
 
+/* ---- triangle meshes: the object built on the device ------------------------------- */
+/* (new symbols only: NR_ABI_VERSION stays 3, nr_stats is unchanged; named nr_mesh_* like everything
+ * added since nr_trimesh_distance -- see the remesh section above)
+ * nr_mesh_create_device is nr_trimesh_create for vertices and triangles that are in device
+ * memory -- the meshes of nr_extract_mesh*, nr_compose_extract_mesh* and nr_mesh_remesh*: table,
+ * order, tree, moments and area table are made by kernels, no geometry crosses to the host, and every
+ * query above takes the object unchanged.  nr_mesh_download returns what any nr_trimesh holds.
+ *
+ * The contract of a device-built mesh.  libm's atan2, nth_element's order inside a leaf and one
+ * sequential f64 sum over all triangles cannot be had from kernels, so a device-built mesh has its
+ * own contract, to the bit (tests/trimesh_device_ref.py restates it in numpy): node layout, words,
+ * slack, box growth, the moments' formulas and the area table's T and L are those above; what
+ * differs is this.  f64 from the f32 coordinates, one rounding per operation, no contraction; dot and
+ * len are nr_mesh_winding's: dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z, len(u) =
+ * (double)sqrtf((float)dot(u, u)).
+ *  1. Bound.  lo, hi and the largest |coordinate| over all nv vertices, exact, -0 below +0;
+ *     slack = 2^-18 (largest |coordinate| + largest axis extent) in f64, as above.
+ *  2. Table, each entry rounded to f32 once.
+ *     face    n = (b - a) x (c - a); (0, 0, 0), the triangle dead, if n is (0, 0, 0) or not finite;
+ *             else s = max |n_k|, m = n / s (three divisions), the entry m / len(m) (three more).
+ *     edge    as above: the sum of the f64 face normals of every use of the undirected edge, in
+ *             ascending triangle index.
+ *     vertex  the sum over the live triangles that use the vertex, ascending triangle index, of
+ *             angle * face normal (per component s = s + angle * n), angle = h(len(u x v), dot(u, v))
+ *             with h of nr_mesh_winding's step 2 (the angle is h, not 2 h).
+ *     closed  as above.
+ *  3. Order.  Centroid x_k = ((a_k + b_k) + c_k) / 3.0f in f32; key = the NR_ORDER_MORTON key of x in
+ *     the box [lo, hi] of 1 (rule 6 of the fitting samples; an axis of no extent gives cell 0); a dead
+ *     triangle's key is 2^30.  order = the first ntl entries of the stable ascending sort of the
+ *     keys, ties by triangle index; ntl = the live triangles.
+ *  4. Tree.  The node of positions [first, first + count) is a leaf if count <= leaf, else it splits
+ *     at half = (count + 1) / 2; preorder.  Words 3 and 7 are therefore those of the host tree for
+ *     the same (ntl, leaf), and depth <= ceil(log2 ntl) + 1.  A box is the exact f32 bound of the
+ *     node's corners, grown by slack in f64 and rounded outward as above.  ntl = 0: the one empty
+ *     leaf.
+ *  5. Moments.  Per position A_t and x_t as above, |A_t| = len(A_t).  A leaf's raw sums, sequential
+ *     in position order: sa = sum |A|, sx = sum |A| x, mx = sum x, N = sum A, P = sum A x^T; an inner
+ *     node's are left + right, one addition per entry.  c as above from sa, sx, mx and the count,
+ *     rounded to f32; M = P - N c^T about the rounded c, one product and one subtraction per entry;
+ *     S from M and the record as above; R2 as above (a maximum: no order).
+ *  6. Area table.  |A_p| as in 5; C_p = base[p / 256] + the sequential running sum inside p's block
+ *     of 256 positions, base = the sequential exclusive sum of the blocks' totals, C_last the sum
+ *     after the last block; T and L as above.
+ *
+ *  - nr_mesh_create_device: limits and errors as nr_trimesh_create; indices and vertices are
+ *    checked by a kernel (NR_E_INVALID, *out = NULL, nothing kept).  The arrays are read during the
+ *    call only.  The host reads back two records of 128 bytes (the error flags, the bound, ntl;
+ *    closed and L) and makes the tree's shape, a function of (ntl, leaf), between them; the call
+ *    returns when the mesh is built.  Two radix sorts (nr_points_order's passes) of nt and 3 nt
+ *    keys, one launch per level of the tree: 36 + depth launches.  Scratch held by the owner context
+ *    and reused: 98 bytes per triangle and 204 bytes per node of the tree nt live triangles would
+ *    give (leaf 8: fewer than nt / 2 nodes, so at most 200 bytes per triangle; leaf 1: 2 nt - 1
+ *    nodes).  stats (may be NULL): ray_steps = nt, launches, ms_total.
+ *  - nr_mesh_download: what the object holds, however built; any pointer may be NULL.  nodes
+ *    [nodes of nr_trimesh_info][8], order [ntl], moments [nodes][16], table [nt][7][3], thresholds
+ *    [ntl] (size them by nt and 2 nt nodes, or call once for ntl).  For a host-built mesh these are
+ *    nr_mesh_hierarchy's, nr_trimesh_normals' and nr_mesh_area_table's bytes.  NR_E_INVALID: a
+ *    NULL mesh. */
+int nr_mesh_create_device(nr_ctx *owner, const float *d_vertices /*[nv][3], device*/, long nv,
+                             const int32_t *d_triangles /*[nt][3], device*/, long nt,
+                             int leaf /*0 = 8, else 1..32*/, nr_trimesh **out, nr_stats *stats /*or NULL*/);
+int nr_mesh_download(nr_trimesh *m, float *nodes /*[nnodes][8]*/, int32_t *order /*[ntl]*/,
+                        float *moments /*[nnodes][16]*/, float *table /*[nt][7][3]*/,
+                        uint32_t *thresholds /*[ntl]*/, long *ntl, long *area_last);
+
 /* ---- composed scenes: several networks, placed and combined by CSG ---------------- */
 /* (new symbols and new structs only: NR_ABI_VERSION stays 3, nr_stats is unchanged)
  *
